@@ -7,13 +7,15 @@ gradient buffer over RCCL when N > 1) -> Adam.step, on synthetic
 [B, 4, 256, 256, 16] volumes resident in HBM (config 2: fp32,
 feature_sizes [8..128], B = 2 per GPU).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
-Prints one JSON line (rank 0) with the whole-job voxels/s, the roofline of
-the dominant kernel (HIP-event timing of every launch during a second pass of
-K steps) and the CPU baseline (the oracle restatement of the reference timed
-on this host's cores).
+Prints one JSON line (rank 0) with the whole-job voxels/s and ms_per_step of
+the K timed steps.  A plain run does nothing else.  --full adds the roofline
+of the dominant kernel (HIP-event timing of every launch during a second pass
+of K steps), the per-layer table, the idle-queue enqueue cost and the CPU
+baseline (the oracle restatement of the reference timed on this host's cores).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -84,6 +86,38 @@ def synth_inputs(B, seed, device):
     mask = (torch.rand((B, 1) + TILE, generator=g) < 0.5).half()
     pwl = (torch.rand((B, 1) + TILE, generator=g) * 11.0).half()
     return x.to(device), mask.to(device), pwl.to(device)
+
+
+DUMP_MAX_ELEMS = 4 << 20   # per array: 16 MB of float32, so the few arrays of a run stay under 64 MB
+
+
+def snapshot(arrays):
+    """Host copies (float32; float64 stays) of {name: tensor} for
+    --dump-outputs, taken right after the timed steps, before anything else
+    runs on the device.  An array of more than DUMP_MAX_ELEMS elements is cut
+    to a fixed, seeded sample of its elements (sorted flat indices), the same
+    in every run."""
+    snap = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(20240)
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        snap[name] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+    return snap
+
+
+def write_dump(path, snap):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in snap.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
+def flat_grads(model):
+    return torch.cat([p.grad.detach().reshape(-1).float() for p in model.parameters()
+                      if p.grad is not None])
 
 
 def cpu_baseline(cfg, x, mask, pwl, budget_s=15.0):
@@ -270,9 +304,11 @@ def infer_main(args):
         mask = seg.predict_segmentation_mask(model, vol_dev, device, use_probability_map=True)
     torch.cuda.synchronize(device)
     el = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        write_dump(args.dump_outputs, snapshot({'mask': mask}))
     vox = INFER_VOLUME[2] * INFER_VOLUME[3] * INFER_VOLUME[4]
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # one tile of the oracle restatement (CPU, B=1, eval) on the host cores
         from oracle import unet_oracle as uo
         threads = max(1, min(16, os.cpu_count() or 1))
@@ -371,7 +407,7 @@ def runet_main(args):
         hcunet_amd.dist.allreduce_gradients(model)
         opt.step()
         state['i'] = i + 1
-        return loss
+        return loss, out
 
     def sync():
         torch.cuda.synchronize(device)
@@ -383,9 +419,12 @@ def runet_main(args):
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, out = step()
     sync()
     el = (time.perf_counter() - t0) / args.steps
+    snap = None
+    if args.dump_outputs and rank == 0:
+        snap = snapshot({'out': out, 'loss': loss, 'grads': flat_grads(model)})
     if world > 1:
         t = torch.tensor([el], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -393,7 +432,7 @@ def runet_main(args):
     vox = world * RUNET_TILE[0] * RUNET_TILE[1] * RUNET_TILE[2]
     roofline = kernels = None
     layers = None
-    if not args.no_kernel_timing and world == 1:
+    if args.full and not args.no_kernel_timing and world == 1:
         _lib.lib().hcu_timing_enable(args.steps * 2048)
         _lib.lib().hcu_timing_detail(1)
         hcunet_amd.chain.TAG_CHAINS = True
@@ -458,7 +497,7 @@ def runet_main(args):
                                    "launches_per_step": v['count'] / args.steps} for k, v in rep.items()),
                                  key=lambda r: -r['ms_per_step'])[:10]}
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         # bounded sample: one fp32 train step of the oracle restatement on the
         # benched 512x512x24 tile (same network, same step; ~10 s on 16 threads)
         from oracle import runet_oracle as ro, loss_oracle as lo
@@ -487,8 +526,10 @@ def runet_main(args):
                        "global_batch": world, "per_gpu_batch": 1, "parallelism": "dp%d" % world,
                        "final_loss": float(loss.item())},
             "roofline": roofline, "cpu_baseline": cpu, "kernels": kernels, "layers": layers}
-    if not args.no_kernel_timing and world == 1:
+    if args.full and not args.no_kernel_timing and world == 1:
         line["step_roofline"] = step_roof
+    if snap is not None:
+        write_dump(args.dump_outputs, snap)
     if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
@@ -501,10 +542,19 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--config', default='2', choices=sorted(CONFIGS))
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-timing', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (model output, '
+                         'loss, flat gradient; float32, a fixed seeded sample of an array above 4 Mi '
+                         'elements) as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beside the headline figure: the per-kernel HIP-event timing '
+                         'pass (roofline, per-layer table), the idle-queue enqueue steps and the CPU '
+                         'baseline; without it only the warm-up and the timed steps run')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave the CPU baseline out')
+    ap.add_argument('--no-kernel-timing', action='store_true',
+                    help='with --full: leave the per-kernel timing pass out')
     ap.add_argument('--idle-steps', type=int, default=7,
-                    help='extra single steps enqueued onto an idle queue after the '
+                    help='with --full: extra single steps enqueued onto an idle queue after the '
                          'timed region (host_enqueue_idle_ms); 0 in profiling passes')
     ap.add_argument('--fresh-input', action='store_true',
                     help='clone the input every step (data-loader pattern; checks graph re-use)')
@@ -553,7 +603,7 @@ def main():
         loss.backward()
         hcunet_amd.dist.allreduce_gradients(model)
         opt.step()
-        return loss
+        return loss, out
 
     def sync():
         torch.cuda.synchronize(device)
@@ -565,7 +615,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, out = step()
     t_enq = time.perf_counter() - t0   # host time to enqueue the K steps
     sync()
     elapsed = time.perf_counter() - t0
@@ -575,11 +625,15 @@ def main():
         elapsed = float(t.item())
     final_loss = float(loss.item())
     ms_per_step = elapsed / args.steps * 1e3
+    snap = None
+    if args.dump_outputs and rank == 0:
+        snap = snapshot({'out': out, 'loss': loss, 'grads': flat_grads(model)})
+    del out
     # host cost of ONE step enqueued onto an idle, synchronised queue (no
     # backpressure from earlier steps): the median of 7 such steps.  If this
     # approaches ms_per_step the step is host-bound on this box.
     idle_enq = []
-    for _ in range(args.idle_steps):
+    for _ in range(args.idle_steps if args.full else 0):
         sync()
         t1 = time.perf_counter()
         step()
@@ -595,7 +649,7 @@ def main():
     tiling['mode'] = _lib.tuning_mode()
     if os.environ.get('HCU_TUNE_SAVE'):
         tiling['saved'] = _lib.tuning_save(os.environ['HCU_TUNE_SAVE'])
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         _lib.lib().hcu_timing_enable(args.steps * 512)
         _lib.lib().hcu_timing_detail(1)
         for _ in range(args.steps):
@@ -651,7 +705,7 @@ def main():
                                  key=lambda r: -r['ms_per_step'])[:8]}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg, x, mask, pwl)
 
     if rank == 0:
@@ -672,12 +726,15 @@ def main():
         # SURVEY §8d per-layer roofline of the whole step (sum over layers of
         # max(bytes / 8 TB/s, flops / dense MFMA peak), hcunet_amd/roofline.py)
         # vs the measured step
-        roof_ms, roof_fl, roof_by = roofline_mod.step_roofline(cfg['kw'], B, TILE, bf16)
-        line["step_roofline"] = {"per_layer_roofline_ms": roof_ms, "measured_ms": ms_per_step,
-                                 "frac": roof_ms / ms_per_step, "flops": roof_fl,
-                                 "compulsory_bytes": roof_by}
+        if args.full:
+            roof_ms, roof_fl, roof_by = roofline_mod.step_roofline(cfg['kw'], B, TILE, bf16)
+            line["step_roofline"] = {"per_layer_roofline_ms": roof_ms, "measured_ms": ms_per_step,
+                                     "frac": roof_ms / ms_per_step, "flops": roof_fl,
+                                     "compulsory_bytes": roof_by}
         if layer_rows is not None:
             line["layers"] = layer_rows
+        if snap is not None:
+            write_dump(args.dump_outputs, snap)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

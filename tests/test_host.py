@@ -217,3 +217,24 @@ def test_bench_rocprof_names_map_to_timed_labels():
         assert bench.rocprof_avg_us(kern, cfg, 'serial_') is not None, (cfg, kern)
         assert bench.load_traffic(kern, cfg) is not None, (cfg, kern)
     assert bench.rocprof_avg_us('bconv_kernel<bf16,1,1,4,8>', 'runet') is not None
+
+
+def test_bench_dump_outputs_snapshot(tmp_path):
+    """bench.py --dump-outputs: small arrays keep their shape and become
+    float32 (float64 stays), an array above the cap is cut to a fixed sample of
+    its elements that is the same in every call, and the files load back."""
+    import numpy as np
+    import bench
+    big = torch.arange(bench.DUMP_MAX_ELEMS + 1000, dtype=torch.float32)
+    arrays = {'out': torch.arange(24.0).reshape(2, 3, 4).bfloat16(), 'loss': torch.tensor(1.5, dtype=torch.float64),
+              'big': big}
+    s1, s2 = bench.snapshot(arrays), bench.snapshot(arrays)
+    assert s1['out'].dtype == np.float32 and s1['out'].shape == (2, 3, 4)
+    assert s1['loss'].dtype == np.float64 and s1['loss'].shape == ()
+    assert s1['big'].shape == (bench.DUMP_MAX_ELEMS,) and s1['big'].dtype == np.float32
+    assert (np.diff(s1['big']) >= 0).all() and s1['big'].max() < big.numel()   # sorted indices into big
+    assert all((s1[k] == s2[k]).all() for k in s1)
+    assert sum(a.nbytes for a in s1.values()) <= 64 << 20
+    bench.write_dump(str(tmp_path / 'd'), s1)
+    for k, a in s1.items():
+        np.testing.assert_array_equal(np.load(str(tmp_path / 'd' / (k + '.npy'))), a)

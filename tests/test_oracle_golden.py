@@ -42,6 +42,44 @@ def _cmp(a, g, full, rtol=1e-5, atol=1e-6):
     np.testing.assert_allclose(a, g, rtol=rtol, atol=atol)
 
 
+CANCELLED_ABS = 1e-4    # biases whose exact gradient is 0 (feed a train-mode BatchNorm), as in test_gpu_unet.py
+
+
+def _bn_cancelled(name):
+    return name.endswith('conv1.bias') or name.endswith('conv2.bias') or name.endswith('up_conv.bias')
+
+
+def _cmp_grad(name, a, g32, g64, full, rtol, atol):
+    """One gradient (in full, or its digest) of the fp32 oracle against the
+    reference's fp32 and fp64 runs.  The oracle restates the reference's
+    arithmetic, but the order of torch's CPU reductions follows the host (its
+    vector width and thread count), so every entry has to meet one of two bars:
+    the reference's fp32 value within rtol / atol (the same reduction order), or
+    the reference's fp64 value within 8x the reference's own fp32-vs-fp64
+    deviation (the bar of tests/test_gpu_runet.py; floor 1e-5 of the largest
+    element).  The deviation is taken over the whole tensor (over the 64
+    samples of a digest), per entry for a digest's sum, norm and max.  A bias
+    that feeds a train-mode BatchNorm has the exact gradient 0 (its fp64 value
+    is ~1e-13): the reference's fp32 value there is rounding alone, and the
+    floor is the absolute CANCELLED_ABS that test_gpu_unet.py sets for these."""
+    a = np.asarray(a if full else _digest(a), dtype=np.float64)
+    g32 = np.asarray(g32, dtype=np.float64)
+    g64 = np.asarray(g64, dtype=np.float64)
+    assert a.shape == g32.shape == g64.shape
+    near32 = np.abs(a - g32) <= atol + rtol * np.abs(g32)
+    noise = np.abs(g32 - g64)
+    if full:
+        noise = np.full_like(noise, noise.max())
+        top = np.abs(g64).max()
+    else:
+        noise = np.concatenate([noise[:3], np.full_like(noise[3:], noise[3:].max())])
+        top = abs(g64[2])
+    floor = CANCELLED_ABS if _bn_cancelled(name) else 1e-5 * top
+    near64 = np.abs(a - g64) <= np.maximum(8.0 * noise, floor)
+    bad = ~(near32 | near64)
+    assert not bad.any(), (name, a[bad][:4], g32[bad][:4], g64[bad][:4])
+
+
 def _state_from_golden(d, full, spec):
     if full:
         return {k[5:]: torch.from_numpy(np.array(d[k])) for k in d.files if k.startswith('init/')}
@@ -68,7 +106,7 @@ def test_oracle_matches_reference(name):
         n = str(n)
         g = d['grad/' + n]
         scale = np.abs(g).max() if full else abs(g[2])
-        _cmp(r['grads'][n], g, full, rtol=1e-4, atol=1e-4 * scale + 1e-9)
+        _cmp_grad(n, r['grads'][n], g, d['f64/grad/' + n], full, rtol=1e-4, atol=1e-4 * scale + 1e-9)
     for k in d.files:
         if k.startswith('stats/'):
             _cmp(r['state_after'][k[6:]], d[k], full, rtol=1e-5, atol=1e-6)
@@ -76,7 +114,9 @@ def test_oracle_matches_reference(name):
         n = str(n)
         # Adam moves ~lr per weight; tiny-gradient sign noise may flip a few weights.
         a = r['state_after'][n] if full else None
-        if full:
+        # (a BatchNorm-cancelled bias moves by lr * sign(rounding noise): not
+        # determined by fp32 arithmetic, left out as in test_gpu_unet.py check_adam)
+        if full and not _bn_cancelled(n):
             bad = np.abs(a.numpy() - d['adam/' + n]) > 1e-5
             assert bad.mean() <= 0.02, (n, bad.mean())
     # eval-mode forward after the step, from the reference's own updated state

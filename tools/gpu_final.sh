@@ -90,14 +90,14 @@ done
 fi
 if has bench; then
 for C in 2 3; do
-  timeout -k 10 300 python -u bench.py --config $C --steps 20 --warmup 3 > $O/${TAG}_bench_config$C.json 2> $O/${TAG}_bench_config$C.err \
+  timeout -k 10 300 python -u bench.py --full --config $C --steps 20 --warmup 3 > $O/${TAG}_bench_config$C.json 2> $O/${TAG}_bench_config$C.err \
     || { tail -30 $O/${TAG}_bench_config$C.err; exit 1; }
   cut -c1-400 $O/${TAG}_bench_config$C.json
 done
-timeout -k 10 300 python -u bench.py --infer --steps 3 --warmup 1 > $O/${TAG}_bench_infer.json 2> $O/${TAG}_bench_infer.err \
+timeout -k 10 300 python -u bench.py --full --infer --steps 3 --warmup 1 > $O/${TAG}_bench_infer.json 2> $O/${TAG}_bench_infer.err \
   || { tail -30 $O/${TAG}_bench_infer.err; exit 1; }
 cut -c1-300 $O/${TAG}_bench_infer.json
-timeout -k 10 300 python -u bench.py --runet --steps 5 --warmup 2 > $O/${TAG}_bench_runet.json 2> $O/${TAG}_bench_runet.err \
+timeout -k 10 300 python -u bench.py --full --runet --steps 5 --warmup 2 > $O/${TAG}_bench_runet.json 2> $O/${TAG}_bench_runet.err \
   || { tail -30 $O/${TAG}_bench_runet.err; exit 1; }
 cut -c1-300 $O/${TAG}_bench_runet.json
 fi

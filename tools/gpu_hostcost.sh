@@ -16,6 +16,6 @@ HCU_HOST_PROF=1 timeout -k 10 120 python -u tools/host_split.py --config $C > $O
 grep -v amdgpu.ids $O/${TAG}_host_split_$C.txt
 done
 for C in 2 3; do
-timeout -k 10 300 python -u bench.py --config $C --steps 30 --warmup 5 --no-cpu-baseline --no-kernel-timing > $O/${TAG}_b$C.json 2> $O/${TAG}_b$C.err || { tail -20 $O/${TAG}_b$C.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --config $C --steps 30 --warmup 5 --no-cpu-baseline --no-kernel-timing > $O/${TAG}_b$C.json 2> $O/${TAG}_b$C.err || { tail -20 $O/${TAG}_b$C.err; exit 1; }
 python3 -c "import json;d=json.loads(open('$O/${TAG}_b$C.json').read().strip().splitlines()[-1]);print('config $C', d['ms_per_step'], d['config']['host_enqueue_ms_per_step'], d['config']['host_enqueue_idle_ms'])"
 done
