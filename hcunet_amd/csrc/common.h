@@ -466,6 +466,42 @@ struct WGradFinalize {
   int J[3], SS[3];                          // mode 3: taps per phase, stride
   int accumulate;
 };
+// The shape fields of a mode-0 (Conv3d) finalize; the slab fields (KB, Mtot,
+// Ntot) and partial / dw / db / accumulate are the caller's.
+inline WGradFinalize wgf_conv(int T, int Cout, int Cin_g, int groups, int fold_mod, int part_c,
+                              int part_cs, int ACs) {
+  WGradFinalize f{};
+  f.mode = 0;
+  f.T = T;
+  f.Cout = Cout;
+  f.Cin_g = Cin_g;
+  f.groups = groups;
+  f.fold_mod = fold_mod;
+  f.part_c = part_c;
+  f.part_cs = part_cs;
+  f.ACs = ACs;
+  return f;
+}
+// The pointwise weight-gradient kernel's arguments for the slabs the 1x1x1
+// finalize `f` sums (f.KB blocks, one slab each at f.partial): A [nvox][ACs],
+// G [nvox][GCs].  (A of channel parts: the caller adds nparts / pcs / Ap.)
+inline PwWgArgs pw_wgrad_args(const WGradFinalize &f, const void *A, const void *G, long nvox,
+                              int ACs, int GCs) {
+  PwWgArgs g{};
+  g.A = static_cast<const uint16_t *>(A);
+  g.G = static_cast<const uint16_t *>(G);
+  g.partial = const_cast<float *>(f.partial);
+  g.nvox = nvox;
+  g.per_block = (nvox + f.KB - 1) / f.KB;
+  g.ACs = ACs;
+  g.GCs = GCs;
+  g.ACR = f.ACs;
+  g.GCR = f.Ntot;
+  g.Mtot = f.Mtot;
+  g.Ntot = f.Ntot;
+  g.bias_row = f.Mtot > f.T * f.ACs ? 1 : 0;
+  return g;
+}
 int launch_wgrad_finalize(const WGradFinalize &f, hipStream_t s);
 constexpr int kWgfBatch = 24;   // finalize jobs per launch (kernel argument < 4 KB)
 int launch_wgrad_finalize_batch(const WGradFinalize *fs, int n, hipStream_t s);

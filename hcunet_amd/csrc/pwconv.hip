@@ -441,40 +441,18 @@ extern "C" int hcu_pw_conv_backward(const void *const *parts, int nparts, int pa
       if (int e = hcu::launch_pw(a, s)) return e;
   }
   // weight / bias gradient: slabs (one per block) + the fixed-order finalize
-  const int KB = hcu::pw_wgrad_blocks(nvox);
-  hcu::PwWgArgs g{};
-  g.G = static_cast<const uint16_t *>(dout);
-  g.A = static_cast<const uint16_t *>(parts[0]);
-  g.partial = work;
-  g.nvox = nvox;
-  g.per_block = (nvox + KB - 1) / KB;
-  g.ACs = ACs;
-  g.GCs = out_cs;
-  g.ACR = ACs;   // (slots: the finalize maps torch channels to them)
-  g.GCR = Cout;
-  g.Mtot = ACs + 1;
-  g.Ntot = Cout;
-  g.bias_row = 1;
-  g.nparts = nparts;
-  g.pcs = part_cs;
-  for (int i = 0; i < nparts; ++i) g.Ap[i] = static_cast<const uint16_t *>(parts[i]);
-  if (int e = hcu::launch_pw_wgrad(g, KB, s)) return e;
-  hcu::WGradFinalize f{};
+  hcu::WGradFinalize f = hcu::wgf_conv(1, Cout, Cin, 1, Cin, part_c, part_cs, ACs);
   f.partial = work;
   f.dw = dw;
   f.db = db;
-  f.KB = KB;
-  f.Mtot = g.Mtot;
-  f.Ntot = g.Ntot;
-  f.T = 1;
-  f.mode = 0;
-  f.Cout = Cout;
-  f.Cin_g = Cin;
-  f.groups = 1;
-  f.fold_mod = Cin;
-  f.part_c = part_c;
-  f.part_cs = part_cs;
-  f.ACs = ACs;
+  f.KB = hcu::pw_wgrad_blocks(nvox);
+  f.Mtot = ACs + 1;   // (rows: every slot -- the finalize maps torch channels to them -- and the bias)
+  f.Ntot = Cout;
   f.accumulate = accumulate;
+  hcu::PwWgArgs g = hcu::pw_wgrad_args(f, parts[0], dout, nvox, ACs, out_cs);
+  g.nparts = nparts;
+  g.pcs = part_cs;
+  for (int i = 0; i < nparts; ++i) g.Ap[i] = static_cast<const uint16_t *>(parts[i]);
+  if (int e = hcu::launch_pw_wgrad(g, f.KB, s)) return e;
   return hcu::launch_wgrad_finalize(f, s);
 }

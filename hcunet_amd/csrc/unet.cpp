@@ -88,6 +88,61 @@ struct BNLayer {
   double count = 0;
 };
 
+// One planned weight gradient: the kernel's arguments, the finalize of its
+// slabs (the shape fields; run_wgrad adds the pointers) and the floats it takes
+// from the slab arena.  The plan sizes the arena from `slab` / `pw_slab`, and
+// run_wgrad requests exactly those.
+struct WGradJob {
+  WGradArgs w{};
+  WGradFinalize f{};
+  bool on = false;       // planned (ConvTLayer's optional forms)
+  // > 0: a bf16 1x1x1 Conv3d whose input carries no BatchNorm+ReLU runs the
+  // pointwise VALU form (pw_wgrad_kernel) on this many blocks, one slab each
+  int pw_blocks = 0;
+  size_t slab = 0, pw_slab = 0;   // slab floats of the planned kernel / of the pointwise form
+};
+
+long wgrad_gvox(const WGradArgs &w) { return (long)w.B * w.GX * w.GY * w.GZ; }
+
+// The job of a planned kernel `w` with the finalize shape `f`.
+WGradJob wgrad_job(const WGradArgs &w, WGradFinalize f) {
+  WGradJob j;
+  j.w = w;
+  f.KB = w.KB;
+  f.Mtot = w.Mtot;
+  f.Ntot = w.Ntot;
+  j.f = f;
+  j.on = true;
+  j.slab = wgrad_partial_floats(w);
+  return j;
+}
+
+// What a plan's kernels need from scratch besides the activations: every
+// region is sized for the largest request of its kind.
+struct ScratchNeed {
+  size_t wprep = 0, part = 0, kpart = 0;
+  size_t slab = 0;   // the largest single request to the slab arena
+  // reduction rows in `part` (BatchNorm statistics, column sums)
+  void rows(size_t floats) { part = std::max(part, floats); }
+  // a convolution: its weight image, its K-split partials and `stat` floats
+  // per (row, column) of epilogue statistics
+  void conv(const GConvArgs &a, int stat = 0) {
+    wprep = std::max(wprep, wprep_floats(a));
+    kpart = std::max(kpart, conv_partial_floats(a));
+    rows((size_t)gconv_rows(a) * a.CoutW * stat);
+  }
+  // an arena request (Ctx::slab)
+  void arena(size_t floats) { slab = std::max(slab, floats); }
+  // a weight gradient: the arena holds either form's slabs (`part` has always
+  // been sized for the planned kernel's too, which the per-op entry points use)
+  void job(const WGradJob &j) {
+    rows(j.slab);
+    arena(std::max(j.slab, j.pw_slab));
+  }
+  // floats of the arena: every request fits, `floor` floats for batching finalizes
+  size_t arena_floats(size_t floor) const { return std::max({part, slab, floor}); }
+};
+
 struct ConvLayer {
   std::string name;  // layer tag for per-layer timing ("d0.c1", "u3.c2", ...)
   int Cout = 0, Cin_g = 0, groups = 1, fold_mod = 0, E = 0, T = 0;
@@ -102,12 +157,11 @@ struct ConvLayer {
   bool s2b = false;
   int L3[3] = {1, 1, 1};                   // lattice (= D) of the s2b form
   bool pw = false;                         // bf16 1x1x1, no BatchNorm input: pwconv.hip (forward, dgrad)
-  bool pw_wg = false;                      // ... and its weight gradient (pw_wgrad_kernel)
   Dims sub_in, sub_out;                    // sub-grid tensors (batch B*D)
   int64_t w_off = 0, b_off = 0;
   Dims in, out;
   GConvArgs fwd{}, dgrad{};
-  WGradArgs wg{};
+  WGradJob wg;
   BNLayer bn;
   size_t y_off = 0;
   size_t wf_off = 0, wd_off = 0;  // prepared fwd / dgrad weight images in `saved`
@@ -119,25 +173,24 @@ struct ConvTLayer {
   int K[3], S[3];
   int64_t w_off = 0, b_off = 0;
   Dims in, out;
+  Dims full;            // the output before the crop of a padded layer (== out without padding)
   std::vector<GConvArgs> phases;
   std::vector<int> pJ;  // 6 ints per phase: px,py,pz,Jx,Jy,Jz
   bool fused = false;   // kernel % stride == 0: all phases in one GEMM (N = phase x Cout)
   GConvArgs fwdf{};
   GConvArgs dgrad{};
-  WGradArgs wg{};
+  WGradJob wg;   // rows ci, columns (tap, co): every layer
   // the weight gradient of the phase-folded forward (WGradArgs::nph: phases
   // as extra columns; the bias from the column-sum rows of dU), fp32 U-Net
   // decoders with kernel % stride == 0 and Cout % 4 == 0
-  WGradArgs wgp{};
-  bool wg_phase = false;
+  WGradJob wgp;
   // layer chains, bf16, no BatchNorm+ReLU applied to the input: the weight
   // gradient as the Conv3d weight gradient of the input-gradient convolution
   // (rows (tap, co) over the strided dU halo, columns ci over x; finalize
   // mode 0 with Cout = Cin, Cin_g = Cout -- the [Cin][Cout][K] layout of a
   // ConvTranspose3d weight is a Conv3d weight's [Cout][Cin][K]): every tap in
   // one block, instead of a (tap, co)-column GEMM with one 16-row subtile
-  WGradArgs wgs{};
-  bool wg_swap = false;
+  WGradJob wgs;
   size_t u_off = 0;
   size_t wf_off = 0, wd_off = 0;   // prepared weights in `saved` (fused fwd, dgrad)
   std::vector<size_t> wph_off;     // per-phase fwd weights when not fused
@@ -230,8 +283,18 @@ void set_pw(ConvLayer &L, const Dims &in, int cin_total) {
   L.pw = pw_supported(in.Cs, L.out.Cs, L.Cout, false) &&
          (!L.has_dgrad || pw_supported(in.Cs, L.out.Cs, L.Cout, true));
   // (the slab layout is bwgrad's taps_rows one, planned in L.wg)
-  L.pw_wg = L.wg.use_bw && L.wg.taps_rows && L.wg.ACs == in.Cs && L.wg.GCs == L.out.Cs &&
-            pw_wgrad_supported(in.Cs, L.out.Cs);
+  WGradJob &j = L.wg;
+  if (j.w.use_bw && j.w.taps_rows && j.w.ACs == in.Cs && j.w.GCs == L.out.Cs &&
+      pw_wgrad_supported(in.Cs, L.out.Cs)) {
+    j.pw_blocks = pw_wgrad_blocks(wgrad_gvox(j.w));
+    j.pw_slab = (size_t)j.pw_blocks * j.w.Mtot * j.w.Ntot;
+  }
+}
+
+// The weight-gradient job of a Conv3d layer whose kernel is planned in `w`.
+WGradJob conv_wgrad_job(const ConvLayer &L, const WGradArgs &w) {
+  return wgrad_job(w, wgf_conv(L.T, L.Cout, L.Cin_g, L.groups, L.fold_mod, L.part_c, L.part_cs,
+                               wgrad_slab_acs(w)));
 }
 
 // Conv3d with stride / zero padding (nn.Conv3d(..., stride, padding), the
@@ -293,7 +356,7 @@ int setup_conv_general(ConvLayer &L, const Dims &in, int Cout, int groups, int f
     if (!ef && !ed && !ew) {
       L.fwd = f;
       L.dgrad = dg;
-      L.wg = w;
+      L.wg = conv_wgrad_job(L, w);
     } else if (!dil || !L.has_dgrad) {
       return ef ? ef : ed ? ed : ew;
     } else {
@@ -329,10 +392,11 @@ int setup_conv_general(ConvLayer &L, const Dims &in, int Cout, int groups, int f
     L.dgrad.py = (L.K[1] - 1) - Pd[1];
     L.dgrad.pz = (L.K[2] - 1) - Pd[2];
     if (int e = plan_c(L.dgrad)) return e;
-    L.wg = wgrad_conv(L.sub_in, L.sub_out, L.K, one);
-    L.wg.apx = Pd[0]; L.wg.apy = Pd[1]; L.wg.apz = Pd[2];
-    compact_slab(L.wg, L, bf);
-    if (int e = bf ? plan_bwgrad(L.wg, kTargetBlocks) : plan_wgrad(L.wg, kTargetBlocks)) return e;
+    WGradArgs w = wgrad_conv(L.sub_in, L.sub_out, L.K, one);
+    w.apx = Pd[0]; w.apy = Pd[1]; w.apz = Pd[2];
+    compact_slab(w, L, bf);
+    if (int e = bf ? plan_bwgrad(w, kTargetBlocks) : plan_wgrad(w, kTargetBlocks)) return e;
+    L.wg = conv_wgrad_job(L, w);
   }
   L.bn.C = Cout;
   L.bn.Cs = L.out.Cs;
@@ -376,9 +440,10 @@ int setup_conv(ConvLayer &L, const Dims &in, int Cout, int groups, int fold_mod,
   L.dgrad = gconv_conv_dgrad(in, L.out, K, D, L.E);
   if (int e = bf ? plan_bconv(L.dgrad, kTargetBlocks) : plan_conv_fp32(L.dgrad, kTargetBlocks))
     return e;
-  L.wg = wgrad_conv(in, L.out, K, D);
-  compact_slab(L.wg, L, bf);
-  if (int e = bf ? plan_bwgrad(L.wg, kTargetBlocks) : plan_wgrad(L.wg, kTargetBlocks)) return e;
+  WGradArgs w = wgrad_conv(in, L.out, K, D);
+  compact_slab(w, L, bf);
+  if (int e = bf ? plan_bwgrad(w, kTargetBlocks) : plan_wgrad(w, kTargetBlocks)) return e;
+  L.wg = conv_wgrad_job(L, w);
   L.bn.C = Cout;
   L.bn.Cs = L.out.Cs;
   L.bn.count = (double)L.out.vox();
@@ -387,8 +452,12 @@ int setup_conv(ConvLayer &L, const Dims &in, int Cout, int groups, int fold_mod,
 }
 
 
+// pad (layer chains; null: none): ConvTranspose3d padding, the crop of the full
+// output.  The forward writes the full output (into scratch) and crops it;
+// the backward reads the cropped gradient at offset pad (zero outside it).
+// swap: also plan the swapped weight-gradient form (ConvTLayer::wgs).
 int setup_convt(ConvTLayer &u, const Dims &cur, int o, const int K[3], const int S[3],
-                size_t &max_wprep, size_t &max_part, size_t &max_kpart) {
+                const int *pad, bool swap, ScratchNeed &need) {
   const int f = cur.C;
   u.Cin = f;
   u.Cout = o;
@@ -401,7 +470,13 @@ int setup_convt(ConvTLayer &u, const Dims &cur, int o, const int K[3], const int
   u.in = cur;
   const int ux = (cur.X - 1) * u.S[0] + u.K[0], uy = (cur.Y - 1) * u.S[1] + u.K[1],
             uz = (cur.Z - 1) * u.S[2] + u.K[2];
-  u.out = mkdims(cur.B, ux, uy, uz, o, cur.es);
+  u.full = mkdims(cur.B, ux, uy, uz, o, cur.es);
+  const int P[3] = {pad ? pad[0] : 0, pad ? pad[1] : 0, pad ? pad[2] : 0};
+  for (int d = 0; d < 3; ++d)
+    if (P[d] < 0) return fail(HCU_ERR_INVALID, "ConvTranspose3d: negative padding");
+  const int cx = ux - 2 * P[0], cy = uy - 2 * P[1], cz = uz - 2 * P[2];   // the cropped output
+  if (cx < 1 || cy < 1 || cz < 1) return fail(HCU_ERR_SHAPE, "ConvTranspose3d: output size is too small");
+  u.out = mkdims(cur.B, cx, cy, cz, o, cur.es);
   const bool bf = cur.es == 2;
   u.phases.clear();
   u.pJ.clear();
@@ -429,15 +504,12 @@ int setup_convt(ConvTLayer &u, const Dims &cur, int o, const int K[3], const int
     if (o % cv) a.cph = round_up(o, cv);
     if (bf) {
       if (int e = plan_bconv(a, kTargetBlocks)) return e;
-      u.fwdf = a;
-      max_wprep = std::max(max_wprep, wprep_floats(a));
-      max_kpart = std::max(max_kpart, conv_partial_floats(a));
-    } else if (plan_conv_fp32(a, kTargetBlocks) == 0 && (a.use_bconv || a.use_conv2)) {
-      u.fwdf = a;
-      max_wprep = std::max(max_wprep, wprep_floats(a));
-      max_kpart = std::max(max_kpart, conv_partial_floats(a));
-    } else {
+    } else if (plan_conv_fp32(a, kTargetBlocks) != 0 || !(a.use_bconv || a.use_conv2)) {
       u.fused = false;
+    }
+    if (u.fused) {
+      u.fwdf = a;
+      need.conv(a);
     }
   }
   for (int qx = 0; qx < (bf ? 0 : u.S[0]); ++qx)
@@ -462,12 +534,13 @@ int setup_convt(ConvTLayer &u, const Dims &cur, int o, const int K[3], const int
         u.phases.push_back(a);
         const int pj[6] = {qx, qy, qz, Jx, Jy, Jz};
         u.pJ.insert(u.pJ.end(), pj, pj + 6);
-        max_wprep = std::max(max_wprep, (size_t)Jx * Jy * Jz * a.ICs * a.CoutW);
+        need.conv(a);
       }
   {  // dgrad: strided correlation of dU with W[ci][co][t]
     GConvArgs a{};
     a.B = cur.B;
-    a.IX = ux; a.IY = uy; a.IZ = uz; a.ICs = u.out.Cs;
+    a.IX = cx; a.IY = cy; a.IZ = cz; a.ICs = u.out.Cs;
+    a.px = P[0]; a.py = P[1]; a.pz = P[2];
     a.OX = cur.X; a.OY = cur.Y; a.OZ = cur.Z;
     a.SX = cur.X; a.SY = cur.Y; a.SZ = cur.Z; a.OCs = cur.Cs; a.Cout = f;
     a.osx = a.osy = a.osz = 1;
@@ -476,15 +549,31 @@ int setup_convt(ConvTLayer &u, const Dims &cur, int o, const int K[3], const int
     a.dx = a.dy = a.dz = 1;
     if (int e = bf ? plan_bconv(a, kTargetBlocks) : plan_conv_fp32(a, kTargetBlocks)) return e;
     u.dgrad = a;
-    max_wprep = std::max(max_wprep, wprep_floats(a));
-    max_part = std::max(max_part, (size_t)gconv_rows(a) * a.CoutW * 2);
-    max_kpart = std::max(max_kpart, conv_partial_floats(a));
+    need.conv(a, 2);
   }
+  // the finalize shape of this layer's weight gradient in mode 1 (per tap) / 3 (phases)
+  auto wgf = [&](int mode, const WGradArgs &w) {
+    WGradFinalize fz{};
+    fz.mode = mode;
+    fz.T = u.T;
+    fz.Cin = u.Cin;
+    fz.CoutT = u.Cout;
+    fz.GCs = w.GCs;
+    if (mode == 3) {
+      fz.ACs = w.ACs;
+      for (int d = 0; d < 3; ++d) {
+        fz.J[d] = u.K[d] / u.S[d];
+        fz.SS[d] = u.S[d];
+      }
+    }
+    return fz;
+  };
   {  // wgrad: rows = ci, cols = (t, co)
     WGradArgs w{};
     w.B = cur.B;
     w.AX = cur.X; w.AY = cur.Y; w.AZ = cur.Z; w.ACs = cur.Cs;
-    w.GX = ux; w.GY = uy; w.GZ = uz; w.GCs = u.out.Cs;
+    w.GX = cx; w.GY = cy; w.GZ = cz; w.GCs = u.out.Cs;
+    w.gpx = P[0]; w.gpy = P[1]; w.gpz = P[2];
     w.PX = cur.X; w.PY = cur.Y; w.PZ = cur.Z;
     w.KX = u.K[0]; w.KY = u.K[1]; w.KZ = u.K[2];
     w.asx = w.asy = w.asz = 1;
@@ -493,11 +582,14 @@ int setup_convt(ConvTLayer &u, const Dims &cur, int o, const int K[3], const int
     w.taps_rows = 0;
     w.bias_row = 0;
     if (int e = bf ? plan_bwgrad(w, kTargetBlocks) : plan_wgrad(w, kTargetBlocks)) return e;
-    u.wg = w;
-    max_part = std::max(max_part, wgrad_partial_floats(w));
-    max_part = std::max(max_part, (size_t)chansum_rows(u.out.vox(), u.out.Cs) * u.out.Cs);
+    u.wg = wgrad_job(w, wgf(1, w));
+    need.job(u.wg);
+    // the bias gradient's channel-sum rows (layer chains: an arena slab)
+    const size_t cs = (size_t)chansum_rows(u.out.vox(), u.out.Cs) * u.out.Cs;
+    need.rows(cs);
+    need.arena(cs);
   }
-  u.wg_phase = false;
+  u.wgp = WGradJob{};
   // The weight gradient of the phase-folded forward (stride phases as extra
   // output columns) on wgrad3; the other layers run the per-tap wgrad_kernel.
   // (The U-Net's bias gradient: the column sums of dU, written by the
@@ -521,9 +613,34 @@ int setup_convt(ConvTLayer &u, const Dims &cur, int o, const int K[3], const int
     w.bias_row = 0;
     w.nph = nph; w.phx = u.S[0]; w.phy = u.S[1]; w.phz = u.S[2]; w.GCout = o;
     if (plan_wgrad(w, kTargetBlocks) == 0 && w.v2 == 3) {
-      u.wgp = w;
-      u.wg_phase = true;
-      max_part = std::max(max_part, wgrad_partial_floats(w));
+      u.wgp = wgrad_job(w, wgf(3, w));
+      need.job(u.wgp);
+    } else {
+      set_error("");
+    }
+  }
+  u.wgs = WGradJob{};
+  if (swap) {
+    // dW[ci][co][k] = sum_o x[o][ci] dU[o*S + k - pad][co]
+    WGradArgs v{};
+    v.B = cur.B;
+    v.AX = u.out.X; v.AY = u.out.Y; v.AZ = u.out.Z; v.ACs = u.out.Cs;   // dU (cropped)
+    v.GX = u.in.X; v.GY = u.in.Y; v.GZ = u.in.Z; v.GCs = u.in.Cs;        // x
+    v.PX = u.in.X; v.PY = u.in.Y; v.PZ = u.in.Z;
+    v.KX = u.K[0]; v.KY = u.K[1]; v.KZ = u.K[2];
+    v.asx = u.S[0]; v.asy = u.S[1]; v.asz = u.S[2];
+    v.adx = v.ady = v.adz = 1;
+    v.apx = P[0]; v.apy = P[1]; v.apz = P[2];
+    v.gsx = v.gsy = v.gsz = 1;
+    v.gdx = v.gdy = v.gdz = 1;
+    v.taps_rows = 1;
+    v.bias_row = 0;
+    v.ACr = u.Cout;
+    v.GCr = u.Cin;
+    v.flops = 2.0 * cur.B * u.in.X * u.in.Y * u.in.Z * (double)u.T * u.Cin * u.Cout;
+    if (plan_bwgrad(v, kTargetBlocks) == 0) {
+      u.wgs = wgrad_job(v, wgf_conv(u.T, u.Cin, u.Cout, 1, u.Cout, 0, 0, wgrad_slab_acs(v)));
+      need.job(u.wgs);
     } else {
       set_error("");
     }
@@ -588,8 +705,7 @@ struct hcu_unet_plan {
     int pk[3] = {1, 1, 1};
     Dims pooled;
     size_t pool_off = 0;
-    int crop[3] = {0, 0, 0};       // ConvTranspose3d padding: crop of the full output
-    Dims ufull;
+    int crop[3] = {0, 0, 0};       // ConvTranspose3d padding: crop of the full output (ConvTLayer::full)
     size_t xs_off = 0;             // s2b conv: the sub-lattice input (saved for the weight gradient)
   };
   std::vector<ChainOp> chain;
@@ -598,7 +714,8 @@ struct hcu_unet_plan {
   size_t ufull_off = 0, sub_off[3] = {};   // scratch: full ConvTranspose3d output, sub-lattice temporaries
   size_t max_sub = 0, max_ufull = 0;
   size_t wpart_floats = 0;   // weight-gradient slab arena (deferred, batched finalizes)
-  size_t max_act = 0, max_part = 0, max_wprep = 0, max_kpart = 0;
+  size_t max_act = 0;
+  ScratchNeed need;
   // Captured launch sequences (hipGraph) keyed by the buffers they bake in:
   // forward and backward are fixed kernel sequences, so a replay costs one
   // launch on the host instead of one per kernel.
@@ -649,8 +766,6 @@ struct hcu_unet_plan {
 
 namespace {
 
-size_t prep_floats_fwd(const ConvLayer &L) { return wprep_floats(L.fwd); }
-size_t prep_floats_dgrad(const ConvLayer &L) { return wprep_floats(L.dgrad); }
 // Elements of a prepared weight image (bf16 images hold two per float slot).
 size_t prep_elems(const GConvArgs &a) {
   if (a.use_bconv) return (size_t)wpack_count(wpack_of(a), a.KX * a.KY * a.KZ, a.ICs, a.CoutW);
@@ -659,12 +774,87 @@ size_t prep_elems(const GConvArgs &a) {
 
 void track_conv(hcu_unet_plan &p, const ConvLayer &L) {
   p.max_act = std::max(p.max_act, std::max(L.in.floats(), L.out.floats()));
-  p.max_part = std::max(p.max_part, (size_t)gconv_rows(L.fwd) * L.fwd.CoutW * 4);  // StatRow
-  p.max_part = std::max(p.max_part, wgrad_partial_floats(L.wg));
-  p.max_part = std::max(p.max_part, (size_t)gconv_rows(L.dgrad) * L.dgrad.CoutW * 2);
-  p.max_part = std::max(p.max_part, (size_t)bwd_rows(L.out.vox(), L.out.Cs) * L.out.Cs * 2);
-  p.max_wprep = std::max(p.max_wprep, std::max(prep_floats_fwd(L), prep_floats_dgrad(L)));
-  p.max_kpart = std::max(p.max_kpart, std::max(conv_partial_floats(L.fwd), conv_partial_floats(L.dgrad)));
+  p.need.conv(L.fwd, 4);  // StatRow
+  p.need.conv(L.dgrad, 2);
+  p.need.job(L.wg);
+  p.need.rows((size_t)bwd_rows(L.out.vox(), L.out.Cs) * L.out.Cs * 2);
+}
+
+// Prepared (GEMM-layout) weights of every layer: written once per forward by
+// one batched launch, read by the forward and backward GEMMs.
+void add_prep(hcu_unet_plan &p, Region &saved, int kind, size_t n, int64_t src, const WPack &pk,
+              const int *prm, int np, size_t &off) {
+  PrepJob j{};
+  j.kind = kind;
+  j.bf16 = p.es == 2;
+  j.n = (int64_t)n;
+  j.src = src;
+  off = saved.take_floats(j.bf16 ? (n + 1) / 2 : n);
+  j.dst = (int64_t)(off / sizeof(float));
+  j.pk = pk;
+  std::copy(prm, prm + np, j.p);
+  p.prep_jobs.push_back(j);
+}
+
+void conv_prep(hcu_unet_plan &p, Region &saved, ConvLayer &cl) {
+  const int pf[10] = {cl.Cout, cl.Cin_g, cl.groups, cl.fold_mod, cl.T, cl.fwd.ICs, cl.fwd.CoutW,
+                      cl.part_c ? cl.fwd.ICs : std::min(cl.fold_mod, cl.groups * cl.Cin_g),
+                      cl.part_c, cl.part_cs};
+  add_prep(p, saved, PREP_CONV_FWD, prep_elems(cl.fwd), cl.w_off, wpack_of(cl.fwd), pf, 10, cl.wf_off);
+  if (!cl.has_dgrad) return;
+  const int pd[10] = {cl.Cout, cl.Cin_g, cl.groups, cl.fold_mod, cl.T, cl.dgrad.ICs, cl.dgrad.CoutW,
+                      cl.E, cl.part_c, cl.part_cs};
+  add_prep(p, saved, PREP_CONV_DGRAD, prep_elems(cl.dgrad), cl.w_off, wpack_of(cl.dgrad), pd, 10,
+           cl.wd_off);
+}
+
+void convt_prep(hcu_unet_plan &p, Region &saved, ConvTLayer &u) {
+  if (u.fused) {
+    const int pf[11] = {u.Cin, u.Cout, u.K[0], u.K[1], u.K[2], u.S[0], u.S[1], u.S[2],
+                        u.fwdf.ICs, u.fwdf.CoutW, u.fwdf.cph};
+    add_prep(p, saved, PREP_CONVT_FUSED, prep_elems(u.fwdf), u.w_off, wpack_of(u.fwdf), pf, 11, u.wf_off);
+  } else {
+    u.wph_off.assign(u.phases.size(), 0);
+    for (size_t ph = 0; ph < u.phases.size(); ++ph) {
+      const int *pj = &u.pJ[ph * 6];
+      const GConvArgs &a = u.phases[ph];
+      const int pf[16] = {u.Cin, u.Cout, u.K[0], u.K[1], u.K[2], u.S[0], u.S[1], u.S[2],
+                          pj[0], pj[1], pj[2], pj[3], pj[4], pj[5], a.ICs, a.CoutW};
+      add_prep(p, saved, PREP_CONVT_PHASE, (size_t)pj[3] * pj[4] * pj[5] * a.ICs * a.CoutW, u.w_off,
+               WPack{}, pf, 16, u.wph_off[ph]);
+    }
+  }
+  const int pd[5] = {u.Cin, u.Cout, u.T, u.dgrad.ICs, u.dgrad.CoutW};
+  add_prep(p, saved, PREP_CONVT_DGRAD, prep_elems(u.dgrad), u.w_off, wpack_of(u.dgrad), pd, 5, u.wd_off);
+}
+
+// The forward's images / the input-gradient images only the backward reads.
+void split_prep(hcu_unet_plan &p) {
+  p.prep_fwd.clear();
+  p.prep_bwd.clear();
+  for (const PrepJob &j : p.prep_jobs)
+    (j.kind == PREP_CONV_DGRAD || j.kind == PREP_CONVT_DGRAD ? p.prep_bwd : p.prep_fwd).push_back(j);
+}
+
+// HCU_PLAN_LOG: the weight-gradient kernels with their partial slabs, and the
+// slab arena against the largest request it will get (measurement).
+void plan_log(const hcu_unet_plan &p) {
+  if (!getenv("HCU_PLAN_LOG")) return;
+  auto wlog = [](const std::string &n, const WGradArgs &w) {
+    const char *k = w.use_bw ? "bwgrad" : w.v2 == 3 ? "wgrad3" : w.v2 == 2 ? "wgrad8" : w.v2 == 1 ? "wgrad2" : "wgrad";
+    fprintf(stderr, "wgrad %-8s %-7s KB %5d M %5d N %4d slabs %7.2f MB grid %d x %d x %d\n", n.c_str(), k,
+            w.KB, w.Mtot, w.Ntot, 4e-6 * w.KB * (double)w.Mtot * w.Ntot, w.KB, w.mchunks, w.nchunks);
+  };
+  for (const auto *v : {&p.dc1, &p.dc2, &p.uc1, &p.uc2})
+    for (const ConvLayer &cl : *v) wlog(cl.name, cl.wg.w);
+  for (const ConvTLayer &u : p.up) wlog(u.name, u.wgp.on ? u.wgp.w : u.wg.w);
+  for (const hcu_unet_plan::ChainOp &o : p.chain) {
+    if (o.kind == HCU_CHAIN_CONV) wlog(o.conv.name, o.conv.wg.w);
+    if (o.kind == HCU_CHAIN_CONVT) wlog(o.ct.name, o.ct.wgs.on ? o.ct.wgs.w : o.ct.wg.w);
+  }
+  // (a forward-only plan has no arena and runs no weight gradient)
+  fprintf(stderr, "arena %zu largest slab %zu\n", p.wpart_floats,
+          (p.flags & HCU_PLAN_FORWARD_ONLY) ? (size_t)0 : p.need.slab);
 }
 
 int build_plan(hcu_unet_plan &p) {
@@ -790,7 +980,7 @@ int build_plan(hcu_unet_plan &p) {
     const int level = L - 2 - j;
     const int f = s.features[L - 1 - j], o = s.features[L - 2 - j];
     ConvTLayer &u = p.up[j];
-    if (int e = setup_convt(u, cur, o, s.up_k, s.up_s, p.max_wprep, p.max_part, p.max_kpart)) return e;
+    if (int e = setup_convt(u, cur, o, s.up_k, s.up_s, nullptr, false, p.need)) return e;
     const Dims &skip = p.dc2[level].out;
     if (u.out.X > skip.X || u.out.Y > skip.Y || u.out.Z > skip.Z)
       return fail(HCU_ERR_SHAPE,
@@ -827,63 +1017,19 @@ int build_plan(hcu_unet_plan &p) {
   p.outd = mkdims(p.B, cur.X, cur.Y, cur.Z, p.Co, 4);
   {
     const int R = outconv_bwd_rows(cur.vox(), cur.Cs);
-    p.max_part = std::max(p.max_part, (size_t)R * cur.Cs * 2 + (size_t)R * (p.Co * cur.Cs + p.Co) + 64);
+    p.need.rows((size_t)R * cur.Cs * 2 + (size_t)R * (p.Co * cur.Cs + p.Co) + 64);
   }
-  // Prepared (GEMM-layout) weights of every layer: written once per forward by
-  // one batched launch, read by the forward and backward GEMMs.
   p.prep_jobs.clear();
-  auto add_job = [&](int kind, size_t n, int64_t src, const WPack &pk, const int *prm, int np,
-                     size_t &off) {
-    PrepJob j{};
-    j.kind = kind;
-    j.bf16 = p.es == 2;
-    j.n = (int64_t)n;
-    j.src = src;
-    off = saved.take_floats(j.bf16 ? (n + 1) / 2 : n);
-    j.dst = (int64_t)(off / sizeof(float));
-    j.pk = pk;
-    std::copy(prm, prm + np, j.p);
-    p.prep_jobs.push_back(j);
-  };
-  auto conv_jobs = [&](ConvLayer &cl) {
-    const int pf[8] = {cl.Cout, cl.Cin_g, cl.groups, cl.fold_mod, cl.T, cl.fwd.ICs, cl.fwd.CoutW,
-                       std::min(cl.fold_mod, cl.groups * cl.Cin_g)};
-    add_job(PREP_CONV_FWD, prep_elems(cl.fwd), cl.w_off, wpack_of(cl.fwd), pf, 8, cl.wf_off);
-    const int pd[8] = {cl.Cout, cl.Cin_g, cl.groups, cl.fold_mod, cl.T, cl.dgrad.ICs,
-                       cl.dgrad.CoutW, cl.E};
-    add_job(PREP_CONV_DGRAD, prep_elems(cl.dgrad), cl.w_off, wpack_of(cl.dgrad), pd, 8,
-            cl.wd_off);
-  };
   for (int i = 0; i < L; ++i) {
-    conv_jobs(p.dc1[i]);
-    conv_jobs(p.dc2[i]);
+    conv_prep(p, saved, p.dc1[i]);
+    conv_prep(p, saved, p.dc2[i]);
   }
   for (int j = 0; j + 1 < L; ++j) {
-    ConvTLayer &u = p.up[j];
-    conv_jobs(p.uc1[j]);
-    conv_jobs(p.uc2[j]);
-    if (u.fused) {
-      const int pf[11] = {u.Cin, u.Cout, u.K[0], u.K[1], u.K[2], u.S[0], u.S[1], u.S[2],
-                          u.fwdf.ICs, u.fwdf.CoutW, u.fwdf.cph};
-      add_job(PREP_CONVT_FUSED, prep_elems(u.fwdf), u.w_off, wpack_of(u.fwdf), pf, 11, u.wf_off);
-    } else {
-      u.wph_off.assign(u.phases.size(), 0);
-      for (size_t ph = 0; ph < u.phases.size(); ++ph) {
-        const int *pj = &u.pJ[ph * 6];
-        const GConvArgs &a = u.phases[ph];
-        const int pf[16] = {u.Cin, u.Cout, u.K[0], u.K[1], u.K[2], u.S[0], u.S[1], u.S[2],
-                            pj[0], pj[1], pj[2], pj[3], pj[4], pj[5], a.ICs, a.CoutW};
-        add_job(PREP_CONVT_PHASE, (size_t)pj[3] * pj[4] * pj[5] * a.ICs * a.CoutW, u.w_off,
-                WPack{}, pf, 16, u.wph_off[ph]);
-      }
-    }
-    const int pd[5] = {u.Cin, u.Cout, u.T, u.dgrad.ICs, u.dgrad.CoutW};
-    add_job(PREP_CONVT_DGRAD, prep_elems(u.dgrad), u.w_off, wpack_of(u.dgrad), pd, 5, u.wd_off);
+    conv_prep(p, saved, p.uc1[j]);
+    conv_prep(p, saved, p.uc2[j]);
+    convt_prep(p, saved, p.up[j]);
   }
-  p.prep_fwd.clear();
-  p.prep_bwd.clear();
-  for (const PrepJob &j : p.prep_jobs)
-    (j.kind == PREP_CONV_DGRAD || j.kind == PREP_CONVT_DGRAD ? p.prep_bwd : p.prep_fwd).push_back(j);
+  split_prep(p);
   if (fwd_only) {
     size_t mx = 1;
     for (const auto &a : acts) mx = std::max(mx, a.second);
@@ -909,26 +1055,17 @@ int build_plan(hcu_unet_plan &p) {
     for (int i = 0; i < HCU_NBUF; ++i)
       p.buf_off[i] = scratch.take_floats(fwd_only || i >= p.nbuf ? 0 : p.max_act);
   }
-  p.part_off = scratch.take_floats(p.max_part);
+  p.part_off = scratch.take_floats(p.need.part);
   // the slab arena holds several layers' weight-gradient partials until their
   // finalizes run together (at least one layer's, at most 8 M floats beyond)
-  p.wpart_floats = fwd_only ? 0 : std::max<size_t>(p.max_part, (size_t)8 << 20);
+  p.wpart_floats = fwd_only ? 0 : p.need.arena_floats((size_t)8 << 20);
   p.wpart_off = scratch.take_floats(p.wpart_floats);
-  p.wprep_off = scratch.take_floats(fwd_only ? 0 : p.max_wprep);
-  p.kpart_off = scratch.take_floats(std::max<size_t>(p.max_kpart, 1));
+  p.wprep_off = scratch.take_floats(fwd_only ? 0 : p.need.wprep);
+  p.kpart_off = scratch.take_floats(std::max<size_t>(p.need.kpart, 1));
   for (int j = 0; j + 1 < L; ++j)
     p.colsum_off[j] = scratch.take_floats(fwd_only ? 0 : (size_t)gconv_rows(p.uc1[j].dgrad) * p.uc1[j].dgrad.CoutW * 4);
   p.scratch_bytes = scratch.off;
-  if (getenv("HCU_PLAN_LOG")) {   // weight-gradient kernels and their partial slabs (measurement)
-    auto wlog = [](const std::string &n, const WGradArgs &w) {
-      const char *k = w.use_bw ? "bwgrad" : w.v2 == 3 ? "wgrad3" : w.v2 == 2 ? "wgrad8" : w.v2 == 1 ? "wgrad2" : "wgrad";
-      fprintf(stderr, "wgrad %-8s %-7s KB %5d M %5d N %4d slabs %7.2f MB grid %d x %d x %d\n", n.c_str(), k,
-              w.KB, w.Mtot, w.Ntot, 4e-6 * w.KB * (double)w.Mtot * w.Ntot, w.KB, w.mchunks, w.nchunks);
-    };
-    for (const auto *v : {&p.dc1, &p.dc2, &p.uc1, &p.uc2})
-      for (const ConvLayer &cl : *v) wlog(cl.name, cl.wg);
-    for (const ConvTLayer &u : p.up) wlog(u.name, u.wg_phase ? u.wgp : u.wg);
-  }
+  plan_log(p);
   return 0;
 }
 
@@ -955,7 +1092,6 @@ struct Ctx {
   char *wimg() const { return wi ? wi : sv; }
   int bf() const { return p.es == 2; }   // bf16 activation storage
   float *part() const { return fptr(sc, p.part_off); }
-  float *wpart() const { return fptr(sc, split ? p.wpart_off : p.part_off); }
   // Weight-gradient slab arena: each layer's partial slabs stay until its
   // finalize runs; finalizes are deferred and launched together (one batched
   // kernel on the branch stream) when the next slab would not fit, and at the
@@ -982,7 +1118,13 @@ struct Ctx {
     return e;
   }
   // Arena space for `floats` (flushing the deferred finalizes first if needed).
+  // A request the whole arena cannot hold is refused: the plan sizes the arena
+  // from the same job records that make the requests (ScratchNeed::arena).
   int slab(size_t floats, float *&ptr) {
+    if (floats > p.wpart_floats)
+      return fail(HCU_ERR_WORKSPACE, "weight-gradient slab of " + std::to_string(floats) +
+                                         " floats exceeds the plan's arena of " +
+                                         std::to_string(p.wpart_floats) + " floats");
     const size_t need = (floats + 63) / 64 * 64;
     if (wp_off + need > p.wpart_floats || pend.size() >= 64)
       if (int e = flush_wgf()) return e;
@@ -1129,56 +1271,60 @@ int conv_backward(Ctx &c, const ConvLayer &L, const float *A, const float *asc,
                   const ConvLayer *bnl = nullptr, int training = 1, bool *bn_done = nullptr,
                   float *colsum = nullptr, bool wg_late = false);
 
+// Runs one planned weight gradient on the branch stream: takes its slab,
+// launches the kernel (the pointwise form for a 1x1x1 job whose input carries
+// no BatchNorm+ReLU) and queues the finalize into dw / db for the next flush
+// (Ctx::slab / end of backward).
+int run_wgrad(Ctx &c, const WGradJob &j, const float *A, const float *a_scale, const float *a_shift,
+              const float *G, float *dw, float *db, int accumulate) {
+  WGradFinalize f = j.f;
+  float *slab = nullptr;
+  if (j.pw_blocks && !a_scale) {
+    if (int e = c.slab(j.pw_slab, slab)) return e;
+    f.partial = slab;
+    f.KB = j.pw_blocks;
+    const PwWgArgs pa = pw_wgrad_args(f, A, G, wgrad_gvox(j.w), j.w.ACs, j.w.GCs);
+    if (int e = launch_pw_wgrad(pa, j.pw_blocks, c.wstream())) return e;
+  } else {
+    if (int e = c.slab(j.slab, slab)) return e;
+    WGradArgs w = j.w;
+    w.A = A;
+    w.a_scale = a_scale;
+    w.a_shift = a_shift;
+    w.G = G;
+    w.partial = slab;
+    if (int e = launch_wgrad(w, c.wstream())) return e;
+    f.partial = slab;
+  }
+  f.dw = dw;
+  f.db = db;
+  f.accumulate = accumulate;
+  return c.pend_wgf(f);
+}
+
+// A bias gradient from column-sum rows [R][W] (mode 2) or forward-statistics
+// rows (mode 4), summed with the batched finalizes.
+WGradFinalize wgf_colsum(int mode, const float *rows, int R, int W, int Cout, float *db, int accumulate) {
+  WGradFinalize f{};
+  f.partial = rows;
+  f.db = db;
+  f.KB = R;
+  f.Mtot = 1;
+  f.Ntot = W;
+  f.mode = mode;
+  f.Cout = Cout;
+  f.accumulate = accumulate;
+  return f;
+}
+
 // The weight-gradient half of conv_backward (forked onto the branch).
 int conv_wgrad(Ctx &c, const ConvLayer &L, const float *A, const float *asc, const float *ash,
                const float *dy, int dy_slot, int accumulate) {
   tag(L.name, "wgrad");
   if (int e = c.fork()) return e;
-  WGradArgs w = L.wg;
-  w.A = A;
-  w.a_scale = asc;
-  w.a_shift = ash;
-  w.G = dy;
-  if (L.pw_wg && !asc) {   // 1x1x1 without a BatchNorm input: the VALU form (pwconv.hip)
-    const long nvox = L.out.vox();
-    w.KB = pw_wgrad_blocks(nvox);
-    if (int e = c.slab(wgrad_partial_floats(w), w.partial)) return e;
-    PwWgArgs pa{};
-    pa.A = reinterpret_cast<const uint16_t *>(A);
-    pa.G = reinterpret_cast<const uint16_t *>(dy);
-    pa.partial = w.partial;
-    pa.nvox = nvox;
-    pa.per_block = (nvox + w.KB - 1) / w.KB;
-    pa.ACs = w.ACs;
-    pa.GCs = w.GCs;
-    pa.ACR = w.ACr > 0 ? w.ACr : w.ACs;
-    pa.GCR = w.GCr > 0 ? w.GCr : w.GCs;
-    pa.Mtot = w.Mtot;
-    pa.Ntot = w.Ntot;
-    pa.bias_row = w.bias_row;
-    if (int e = launch_pw_wgrad(pa, w.KB, c.wstream())) return e;
-  } else {
-    if (int e = c.slab(wgrad_partial_floats(w), w.partial)) return e;
-    if (int e = launch_wgrad(w, c.wstream())) return e;
-  }
-  WGradFinalize f{};
-  f.partial = w.partial;
-  f.dw = c.G + L.w_off;
-  f.db = L.b_off >= 0 ? c.G + L.b_off : nullptr;
-  f.KB = w.KB;
-  f.Mtot = w.Mtot;
-  f.Ntot = w.Ntot;
-  f.T = L.T;
-  f.mode = 0;
-  f.Cout = L.Cout;
-  f.Cin_g = L.Cin_g;
-  f.groups = L.groups;
-  f.fold_mod = L.fold_mod;
-  f.part_c = L.part_c;
-  f.part_cs = L.part_cs;
-  f.ACs = wgrad_slab_acs(w);
-  f.accumulate = accumulate;
-  if (int e = c.pend_wgf(f)) return e;   // finalized with the next flush (Ctx::slab / end of backward)
+  if (int e = run_wgrad(c, L.wg, A, asc, ash, dy, c.G + L.w_off, L.b_off >= 0 ? c.G + L.b_off : nullptr,
+                        accumulate))
+    return e;
   return c.read_done(dy_slot);
 }
 
@@ -1205,7 +1351,9 @@ int conv_backward(Ctx &c, const ConvLayer &L, const float *A, const float *asc,
     w.part_c = L.part_c;
     w.part_cs = L.part_cs;
     w.dgrad = 1;
-    return launch_pw(w, c.s);
+    if (int e = launch_pw(w, c.s)) return e;
+    // (wg_late is not reached here today: its one caller, the U-Net's level-0 conv2, passes bnl)
+    return wg_late ? conv_wgrad(c, L, A, asc, ash, dy, dy_slot, accumulate) : 0;
   }
   GConvArgs a = L.dgrad;
   a.in = dy;
@@ -1715,68 +1863,12 @@ static int enqueue_backward(const hcu_unet_plan &p, const hcu_unet_tensors *t, c
     const BNCoef bp = coef_at(c.sv, prev.bn);
     tag(u.name, "wgrad");
     if (int e = c.fork()) return e;
-    {
-      WGradFinalize fb{};   // the bias: column sums of dU, with the batched finalizes
-      fb.partial = csr;
-      fb.db = c.G + u.b_off;
-      fb.KB = cs_rows;
-      fb.Mtot = 1;
-      fb.Ntot = cs_w;
-      fb.mode = 4;
-      fb.Cout = u.Cout;
-      fb.accumulate = accumulate;
-      if (int e = c.pend_wgf(fb)) return e;
-    }
-    if (u.wg_phase) {   // the weight gradient in one launch (WGradArgs::nph, wgrad3)
-      WGradArgs w = u.wgp;
-      w.A = c.fptr(c.sv, prev.y_off);
-      w.a_scale = bp.scale;
-      w.a_shift = bp.shift;
-      w.G = dU;
-      if (int e = c.slab(wgrad_partial_floats(w), w.partial)) return e;
-      if (int e = launch_wgrad(w, c.wstream())) return e;
-      WGradFinalize f{};
-      f.partial = w.partial;
-      f.dw = c.G + u.w_off;
-      f.db = nullptr;
-      f.KB = w.KB;
-      f.Mtot = w.Mtot;
-      f.Ntot = w.Ntot;
-      f.T = u.T;
-      f.mode = 3;
-      f.Cin = u.Cin;
-      f.CoutT = u.Cout;
-      f.ACs = w.ACs;
-      f.GCs = w.GCs;
-      for (int d = 0; d < 3; ++d) {
-        f.J[d] = u.K[d] / u.S[d];
-        f.SS[d] = u.S[d];
-      }
-      f.accumulate = accumulate;
-      if (int e = c.pend_wgf(f)) return e;
-    } else {
-      WGradArgs w = u.wg;
-      w.A = c.fptr(c.sv, prev.y_off);
-      w.a_scale = bp.scale;
-      w.a_shift = bp.shift;
-      w.G = dU;
-      if (int e = c.slab(wgrad_partial_floats(w), w.partial)) return e;
-      if (int e = launch_wgrad(w, c.wstream())) return e;
-      WGradFinalize f{};
-      f.partial = w.partial;
-      f.dw = c.G + u.w_off;
-      f.db = nullptr;
-      f.KB = w.KB;
-      f.Mtot = w.Mtot;
-      f.Ntot = w.Ntot;
-      f.T = u.T;
-      f.mode = 1;
-      f.Cin = u.Cin;
-      f.CoutT = u.Cout;
-      f.GCs = w.GCs;
-      f.accumulate = accumulate;
-      if (int e = c.pend_wgf(f)) return e;
-    }
+    // the bias: column sums of dU, with the batched finalizes
+    if (int e = c.pend_wgf(wgf_colsum(4, csr, cs_rows, cs_w, u.Cout, c.G + u.b_off, accumulate))) return e;
+    // the weight gradient: in one launch (WGradArgs::nph, wgrad3) where planned, else per tap
+    if (int e = run_wgrad(c, u.wgp.on ? u.wgp : u.wg, c.fptr(c.sv, prev.y_off), bp.scale, bp.shift, dU,
+                          c.G + u.w_off, nullptr, accumulate))
+      return e;
     if (int e = c.read_done(su)) return e;
     tag(u.name, "dgrad");
     if (int e = c.alloc(sd)) return e;
@@ -1926,7 +2018,7 @@ namespace {
 struct OpPlan {
   ConvLayer conv;
   ConvTLayer ct;
-  size_t max_wprep = 0, max_part = 0, max_kpart = 0;
+  ScratchNeed need;
   size_t wprep_off = 0, part_off = 0, kpart_off = 0, scratch_bytes = 0;
 };
 
@@ -1939,21 +2031,22 @@ int make_op(const hcu_conv_desc *d, OpPlan &op) {
       if (d->stride[i] != 1) return fail(HCU_ERR_UNSUPPORTED, "Conv3d: only stride 1 (valid) is supported");
     if (int e = setup_conv(op.conv, in, d->Cout, d->groups, d->Cin, d->Cin, d->k, d->dil, "conv3d"))
       return e;
-    op.max_wprep = std::max(prep_floats_fwd(op.conv), prep_floats_dgrad(op.conv));
-    op.max_part = wgrad_partial_floats(op.conv.wg);
-    op.max_kpart = std::max(conv_partial_floats(op.conv.fwd), conv_partial_floats(op.conv.dgrad));
+    // (the per-op weight gradient always runs the planned kernel, never the pointwise form)
+    op.conv.wg.pw_blocks = 0;
+    op.conv.wg.pw_slab = 0;
+    op.need.conv(op.conv.fwd);
+    op.need.conv(op.conv.dgrad);
+    op.need.job(op.conv.wg);
   } else {
     if (d->groups != 1) return fail(HCU_ERR_UNSUPPORTED, "ConvTranspose3d: groups must be 1");
     for (int i = 0; i < 3; ++i)
       if (d->dil[i] != 1) return fail(HCU_ERR_UNSUPPORTED, "ConvTranspose3d: dilation must be 1");
-    if (int e = setup_convt(op.ct, in, d->Cout, d->k, d->stride, op.max_wprep, op.max_part,
-                            op.max_kpart))
-      return e;
+    if (int e = setup_convt(op.ct, in, d->Cout, d->k, d->stride, nullptr, false, op.need)) return e;
   }
   Region r;
-  op.wprep_off = r.take_floats(op.max_wprep);
-  op.part_off = r.take_floats(op.max_part);
-  op.kpart_off = r.take_floats(std::max<size_t>(op.max_kpart, 1));
+  op.wprep_off = r.take_floats(op.need.wprep);
+  op.part_off = r.take_floats(op.need.part);
+  op.kpart_off = r.take_floats(std::max<size_t>(op.need.kpart, 1));
   op.scratch_bytes = r.off;
   return 0;
 }
@@ -2105,37 +2198,17 @@ int hcu_conv_wgrad_cl(const hcu_conv_desc *d, const float *x, const float *dy, f
   if (int e = check_scratch(op, scratch, scratch_bytes)) return e;
   hipStream_t s = (hipStream_t)stream;
   float *part = reinterpret_cast<float *>((char *)scratch + op.part_off);
-  WGradFinalize f{};
-  WGradArgs w;
-  if (!d->transposed) {
-    const ConvLayer &L = op.conv;
-    w = L.wg;
-    f.mode = 0;
-    f.T = L.T;
-    f.Cout = L.Cout;
-    f.Cin_g = L.Cin_g;
-    f.groups = L.groups;
-    f.fold_mod = L.fold_mod;
-    f.db = dbias;
-  } else {
-    const ConvTLayer &u = op.ct;
-    w = u.wg;
-    f.mode = 1;
-    f.T = u.T;
-    f.Cin = u.Cin;
-    f.CoutT = u.Cout;
-  }
+  // the planned job on the caller's scratch, finalized at once
+  const WGradJob &j = d->transposed ? op.ct.wg : op.conv.wg;
+  WGradArgs w = j.w;
   w.A = x;
   w.G = dy;
   w.partial = part;
   if (int e = launch_wgrad(w, s)) return e;
+  WGradFinalize f = j.f;
   f.partial = part;
   f.dw = dw;
-  f.KB = w.KB;
-  f.Mtot = w.Mtot;
-  f.Ntot = w.Ntot;
-  f.ACs = wgrad_slab_acs(w);
-  f.GCs = w.GCs;
+  f.db = d->transposed ? nullptr : dbias;
   if (int e = launch_wgrad_finalize(f, s)) return e;
   if (d->transposed && dbias) {
     const ConvTLayer &u = op.ct;
@@ -2298,72 +2371,13 @@ int build_chain(hcu_unet_plan &p, const hcu_chain_spec &cs) {
       if (s.groups > 1) return fail(HCU_ERR_UNSUPPORTED, "ConvTranspose3d: groups must be 1");
       ConvTLayer &u = o.ct;
       u.name = nm;
-      if (int e = setup_convt(u, cur, s.out_channels, s.k, s.stride, p.max_wprep, p.max_part, p.max_kpart))
-        return e;
+      const bool swap = bf && !prev_bn && !getenv("HCU_CONVT_NOSWAP");
+      if (int e = setup_convt(u, cur, s.out_channels, s.k, s.stride, s.pad, swap, p.need)) return e;
       u.w_off = s.w_off;
       u.b_off = s.b_off;
-      const Dims full = u.out;
-      int cd[3];
-      const int fd[3] = {full.X, full.Y, full.Z};
-      bool crop = false;
-      for (int d = 0; d < 3; ++d) {
-        o.crop[d] = s.pad[d];
-        if (s.pad[d] < 0) return fail(HCU_ERR_INVALID, "ConvTranspose3d: negative padding");
-        cd[d] = fd[d] - 2 * s.pad[d];
-        if (cd[d] < 1) return fail(HCU_ERR_SHAPE, "ConvTranspose3d: output size is too small");
-        crop = crop || s.pad[d] > 0;
-      }
-      if (crop) {
-        // forward: full output into scratch, then the crop; backward: the
-        // cropped gradient read at offset pad (zero outside it)
-        o.ufull = full;
-        p.max_ufull = std::max(p.max_ufull, full.floats());
-        u.out = mkdims(p.B, cd[0], cd[1], cd[2], s.out_channels, p.es);
-        GConvArgs &a = u.dgrad;
-        a.use_bconv = a.use_conv2 = a.use_conv8 = 0;   // re-planned from scratch
-        a.bes = 0;
-        a.IX = cd[0]; a.IY = cd[1]; a.IZ = cd[2];
-        a.px = s.pad[0]; a.py = s.pad[1]; a.pz = s.pad[2];
-        if (int e = bf ? plan_bconv(a, kTargetBlocks) : plan_conv_fp32(a, kTargetBlocks)) return e;
-        p.max_wprep = std::max(p.max_wprep, wprep_floats(a));
-        p.max_part = std::max(p.max_part, (size_t)gconv_rows(a) * a.CoutW * 2);
-        p.max_kpart = std::max(p.max_kpart, conv_partial_floats(a));
-        WGradArgs &w = u.wg;
-        w.v2 = 0;
-        w.use_bw = 0;
-        w.GX = cd[0]; w.GY = cd[1]; w.GZ = cd[2];
-        w.gpx = s.pad[0]; w.gpy = s.pad[1]; w.gpz = s.pad[2];
-        if (int e = bf ? plan_bwgrad(w, kTargetBlocks) : plan_wgrad(w, kTargetBlocks)) return e;
-        p.max_part = std::max(p.max_part, wgrad_partial_floats(w));
-        p.max_part = std::max(p.max_part, (size_t)chansum_rows(u.out.vox(), u.out.Cs) * u.out.Cs);
-      }
-      u.wg_swap = false;
-      if (bf && !prev_bn && !getenv("HCU_CONVT_NOSWAP")) {
-        // dW[ci][co][k] = sum_o x[o][ci] dU[o*S + k - pad][co]
-        WGradArgs v{};
-        v.B = p.B;
-        v.AX = u.out.X; v.AY = u.out.Y; v.AZ = u.out.Z; v.ACs = u.out.Cs;   // dU (cropped)
-        v.GX = u.in.X; v.GY = u.in.Y; v.GZ = u.in.Z; v.GCs = u.in.Cs;        // x
-        v.PX = u.in.X; v.PY = u.in.Y; v.PZ = u.in.Z;
-        v.KX = u.K[0]; v.KY = u.K[1]; v.KZ = u.K[2];
-        v.asx = u.S[0]; v.asy = u.S[1]; v.asz = u.S[2];
-        v.adx = v.ady = v.adz = 1;
-        v.apx = s.pad[0]; v.apy = s.pad[1]; v.apz = s.pad[2];
-        v.gsx = v.gsy = v.gsz = 1;
-        v.gdx = v.gdy = v.gdz = 1;
-        v.taps_rows = 1;
-        v.bias_row = 0;
-        v.ACr = u.Cout;
-        v.GCr = u.Cin;
-        v.flops = 2.0 * p.B * u.in.X * u.in.Y * u.in.Z * (double)u.T * u.Cin * u.Cout;
-        if (plan_bwgrad(v, kTargetBlocks) == 0) {
-          u.wgs = v;
-          u.wg_swap = true;
-          p.max_part = std::max(p.max_part, wgrad_partial_floats(v));
-        } else {
-          set_error("");
-        }
-      }
+      for (int d = 0; d < 3; ++d) o.crop[d] = s.pad[d];
+      // (a cropped layer's forward writes the full output into scratch)
+      if (o.crop[0] || o.crop[1] || o.crop[2]) p.max_ufull = std::max(p.max_ufull, u.full.floats());
       u.u_off = saved.take_floats(u.out.floats());
       p.max_act = std::max(p.max_act, u.out.floats());
       cur = u.out;
@@ -2379,68 +2393,25 @@ int build_chain(hcu_unet_plan &p, const hcu_chain_spec &cs) {
   // `saved` (or the caller's image buffer: hcu_chain_forward_images)
   const size_t img0 = saved.off;
   p.prep_jobs.clear();
-  auto add_job = [&](int kind, size_t n, int64_t src, const WPack &pk, const int *prm, int np, size_t &off) {
-    PrepJob j{};
-    j.kind = kind;
-    j.bf16 = bf;
-    j.n = (int64_t)n;
-    j.src = src;
-    off = saved.take_floats(j.bf16 ? (n + 1) / 2 : n);
-    j.dst = (int64_t)(off / sizeof(float));
-    j.pk = pk;
-    std::copy(prm, prm + np, j.p);
-    p.prep_jobs.push_back(j);
-  };
   for (ChainOp &o : p.chain) {
-    if (o.kind == HCU_CHAIN_CONV) {
-      ConvLayer &cl = o.conv;
-      const int pf[10] = {cl.Cout, cl.Cin_g, cl.groups, cl.fold_mod, cl.T, cl.fwd.ICs, cl.fwd.CoutW,
-                          cl.part_c ? cl.fwd.ICs : std::min(cl.fold_mod, cl.groups * cl.Cin_g),
-                          cl.part_c, cl.part_cs};
-      add_job(PREP_CONV_FWD, prep_elems(cl.fwd), cl.w_off, wpack_of(cl.fwd), pf, 10, cl.wf_off);
-      if (cl.has_dgrad) {
-        const int pd[10] = {cl.Cout, cl.Cin_g, cl.groups, cl.fold_mod, cl.T, cl.dgrad.ICs, cl.dgrad.CoutW, cl.E,
-                            cl.part_c, cl.part_cs};
-        add_job(PREP_CONV_DGRAD, prep_elems(cl.dgrad), cl.w_off, wpack_of(cl.dgrad), pd, 10, cl.wd_off);
-      }
-    } else if (o.kind == HCU_CHAIN_CONVT) {
-      ConvTLayer &u = o.ct;
-      if (u.fused) {
-        const int pf[11] = {u.Cin, u.Cout, u.K[0], u.K[1], u.K[2], u.S[0], u.S[1], u.S[2],
-                            u.fwdf.ICs, u.fwdf.CoutW, u.fwdf.cph};
-        add_job(PREP_CONVT_FUSED, prep_elems(u.fwdf), u.w_off, wpack_of(u.fwdf), pf, 11, u.wf_off);
-      } else {
-        u.wph_off.assign(u.phases.size(), 0);
-        for (size_t ph = 0; ph < u.phases.size(); ++ph) {
-          const int *pj = &u.pJ[ph * 6];
-          const GConvArgs &a = u.phases[ph];
-          const int pf[16] = {u.Cin, u.Cout, u.K[0], u.K[1], u.K[2], u.S[0], u.S[1], u.S[2],
-                              pj[0], pj[1], pj[2], pj[3], pj[4], pj[5], a.ICs, a.CoutW};
-          add_job(PREP_CONVT_PHASE, (size_t)pj[3] * pj[4] * pj[5] * a.ICs * a.CoutW, u.w_off, WPack{}, pf,
-                  16, u.wph_off[ph]);
-        }
-      }
-      const int pd[5] = {u.Cin, u.Cout, u.T, u.dgrad.ICs, u.dgrad.CoutW};
-      add_job(PREP_CONVT_DGRAD, prep_elems(u.dgrad), u.w_off, wpack_of(u.dgrad), pd, 5, u.wd_off);
-    }
+    if (o.kind == HCU_CHAIN_CONV) conv_prep(p, saved, o.conv);
+    if (o.kind == HCU_CHAIN_CONVT) convt_prep(p, saved, o.ct);
   }
-  p.prep_fwd.clear();
-  p.prep_bwd.clear();
-  for (const PrepJob &j : p.prep_jobs)
-    (j.kind == PREP_CONV_DGRAD || j.kind == PREP_CONVT_DGRAD ? p.prep_bwd : p.prep_fwd).push_back(j);
+  split_prep(p);
   p.img_lo = img0;
   p.img_bytes = saved.off - img0;
   p.saved_bytes = saved.off;
   Region scratch;
   for (int i = 0; i < HCU_NBUF; ++i) p.buf_off[i] = scratch.take_floats(i < p.nbuf ? p.max_act : 0);
-  p.part_off = scratch.take_floats(p.max_part);
-  p.wpart_floats = std::max<size_t>(p.max_part, (size_t)1 << 20);
+  p.part_off = scratch.take_floats(p.need.part);
+  p.wpart_floats = p.need.arena_floats((size_t)1 << 20);
   p.wpart_off = scratch.take_floats(p.wpart_floats);
-  p.wprep_off = scratch.take_floats(p.max_wprep);
-  p.kpart_off = scratch.take_floats(std::max<size_t>(p.max_kpart, 1));
+  p.wprep_off = scratch.take_floats(p.need.wprep);
+  p.kpart_off = scratch.take_floats(std::max<size_t>(p.need.kpart, 1));
   p.ufull_off = scratch.take_floats(p.max_ufull);
   for (size_t &o : p.sub_off) o = scratch.take_floats(p.max_sub);
   p.scratch_bytes = scratch.off;
+  plan_log(p);
   return 0;
 }
 
@@ -2583,7 +2554,7 @@ int enqueue_chain_forward(const hcu_unet_plan &p, const hcu_unet_tensors *t, int
         if (int e = launch_gconv(g, s)) return e;
       }
       if (crop) {
-        const int sd[3] = {o.ufull.X, o.ufull.Y, o.ufull.Z}, dd[3] = {u.out.X, u.out.Y, u.out.Z};
+        const int sd[3] = {u.full.X, u.full.Y, u.full.Z}, dd[3] = {u.out.X, u.out.Y, u.out.Z};
         if (int e = launch_crop_cl(U, c.fptr(c.sv, u.u_off), p.B, sd, dd, o.crop, u.out.Cs, es, s)) return e;
       }
     }
@@ -2687,60 +2658,13 @@ int enqueue_chain_backward(const hcu_unet_plan &p, const hcu_unet_tensors *t, co
         float *cs = nullptr;
         if (int e = c.slab((size_t)R * u.out.Cs, cs)) return e;
         if (int e = launch_chansum(dU, u.out.vox(), u.out.Cs, cs, R, s, bf)) return e;
-        WGradFinalize fb{};
-        fb.partial = cs;
-        fb.db = c.G + u.b_off;
-        fb.KB = R;
-        fb.Mtot = 1;
-        fb.Ntot = u.out.Cs;
-        fb.mode = 2;
-        fb.Cout = u.Cout;
-        fb.accumulate = accumulate;
-        if (int e = c.pend_wgf(fb)) return e;
+        if (int e = c.pend_wgf(wgf_colsum(2, cs, R, u.out.Cs, u.Cout, c.G + u.b_off, accumulate))) return e;
       }
-      if (u.wg_swap && !a.sc) {
-        WGradArgs w = u.wgs;
-        w.A = dU;
-        w.a_scale = w.a_shift = nullptr;
-        w.G = a.x;
-        if (int e = c.slab(wgrad_partial_floats(w), w.partial)) return e;
-        if (int e = launch_wgrad(w, s)) return e;
-        WGradFinalize f{};
-        f.partial = w.partial;
-        f.dw = c.G + u.w_off;
-        f.KB = w.KB;
-        f.Mtot = w.Mtot;
-        f.Ntot = w.Ntot;
-        f.T = u.T;
-        f.mode = 0;
-        f.Cout = u.Cin;
-        f.Cin_g = u.Cout;
-        f.groups = 1;
-        f.fold_mod = u.Cout;
-        f.ACs = wgrad_slab_acs(w);
-        f.accumulate = accumulate;
-        if (int e = c.pend_wgf(f)) return e;
-      } else {
-        WGradArgs w = u.wg;
-        w.A = a.x;
-        w.a_scale = a.sc;
-        w.a_shift = a.sh;
-        w.G = dU;
-        if (int e = c.slab(wgrad_partial_floats(w), w.partial)) return e;
-        if (int e = launch_wgrad(w, s)) return e;
-        WGradFinalize f{};
-        f.partial = w.partial;
-        f.dw = c.G + u.w_off;
-        f.KB = w.KB;
-        f.Mtot = w.Mtot;
-        f.Ntot = w.Ntot;
-        f.T = u.T;
-        f.mode = 1;
-        f.Cin = u.Cin;
-        f.CoutT = u.Cout;
-        f.GCs = w.GCs;
-        f.accumulate = accumulate;
-        if (int e = c.pend_wgf(f)) return e;
+      if (u.wgs.on && !a.sc) {   // rows (tap, co) over dU, columns ci over x
+        if (int e = run_wgrad(c, u.wgs, dU, nullptr, nullptr, a.x, c.G + u.w_off, nullptr, accumulate))
+          return e;
+      } else if (int e = run_wgrad(c, u.wg, a.x, a.sc, a.sh, dU, c.G + u.w_off, nullptr, accumulate)) {
+        return e;
       }
       if (!need_dA) continue;
       tag(u.name, "dgrad");

@@ -215,8 +215,14 @@ def test_convt_chain_bf16_padded_phase_columns(in_cl, swap, monkeypatch):
         assert err <= tol * want.abs().max().item(), (name, err, want.abs().max().item())
 
 
-@pytest.mark.parametrize('cin,cout,part', [(50, 10, 10), (20, 10, 10), (16, 16, 0)])
-def test_pointwise_conv_chain_bf16(cin, cout, part):
+@pytest.mark.parametrize('cin,cout,part,dims', [
+    (50, 10, 10, (24, 20, 6)), (20, 10, 10, (24, 20, 6)), (16, 16, 0, (24, 20, 6)),
+    # 92,160 voxels = 360 pointwise weight-gradient blocks of 97 x 32 floats: the
+    # smallest round shape whose one slab (1,117,440 floats) exceeds the chains'
+    # 1 M-float arena floor, so the arena must be planned from that block count
+    (96, 32, 0, (48, 48, 40)),
+], ids=['50-10-10', '20-10-10', '16-16-0', '96-32-0-48x48x40'])
+def test_pointwise_conv_chain_bf16(cin, cout, part, dims):
     """The streaming 1x1x1 kernels (pwconv.hip) of the bf16 chains: RDCNet's
     mixing convolutions (StackedDilation.out_conv 50 -> 10 and RDCBlock.conv
     20 -> 10 on channel parts of 10 channels in 16 slots, r_unet.py:354-374)
@@ -229,7 +235,7 @@ def test_pointwise_conv_chain_bf16(cin, cout, part):
     conv = nn.Conv3d(cin, cout, 1)
     with torch.no_grad():
         conv.weight.copy_(conv.weight.bfloat16().float())
-    shape = (1, cin, 24, 20, 6)
+    shape = (1, cin) + dims
     x = torch.randn(shape, generator=torch.Generator().manual_seed(12)).bfloat16().float()
     ref = copy.deepcopy(conv).double()
     xr = x.double().requires_grad_(True)
