@@ -670,29 +670,17 @@ __device__ __forceinline__ bool wpack_decode(const WPack &p, I i, int T, int &t,
   ci = chunk * p.CK + (g % C4) * 4 + j;
   return t < T;
 }
-// Conv3d fwd:   wg[t][e][co] (e < ECs, co < CoutW)
-// Conv3d dgrad: wg[t'][co][e] (co < OCs, e < EW), t' = T-1-t
-int launch_prep_conv_fwd(const float *w, float *wg, int Cout, int Cin_g, int groups,
-                         int fold_mod, int T, int ECs, int CoutW, WPack pk, hipStream_t s);
-int launch_prep_conv_dgrad(const float *w, float *wg, int Cout, int Cin_g,
-                           int groups, int fold_mod, int T, int OCs, int EW,
-                           int E, WPack pk, hipStream_t s);
-// ConvTranspose3d fwd phase (px,py,pz): wg[t][ci][co], t over (Jx,Jy,Jz) taps
-int launch_prep_convt_fwd(const float *w, float *wg, int Cin, int Cout, int KX,
-                          int KY, int KZ, int sx, int sy, int sz, int px, int py,
-                          int pz, int Jx, int Jy, int Jz, int ICs, int CoutW,
-                          hipStream_t s);
-// ConvTranspose3d fwd, all phases folded into N (kernel % stride == 0):
-// wg[t'][ci][ph*Cout + co], t' over (Jx,Jy,Jz) taps of the padded correlation.
-int launch_prep_convt_fused(const float *w, float *wg, int Cin, int Cout, int KX, int KY,
-                            int KZ, int sx, int sy, int sz, int ICs, int CoutW, WPack pk,
-                            hipStream_t s);
-// ConvTranspose3d dgrad: wg[t][co][ci] (co < UCs, ci < CinW)
-int launch_prep_convt_dgrad(const float *w, float *wg, int Cin, int Cout, int T,
-                            int UCs, int CinW, WPack pk, hipStream_t s);
 
-// Batched weight preparation: every re-layout of one network step in a few
-// launches (one workgroup row per job) instead of one launch per layer.
+// Weight preparation (prep_all.hip), the one implementation of every
+// re-layout: all jobs of one network step in a few launches (one workgroup row
+// per job); the per-op entry points run one job.  The images, (t, row, column)
+// in the plain or packed layout above:
+//   CONV_FWD     wg[t][e][co]    (e < ECs, co < CoutW), W_eff folded / block-diagonal
+//   CONV_DGRAD   wg[t'][co][e]   (co < OCs, e < EW), t' = T-1-t
+//   CONVT_FUSED  wg[t'][ci][ph*cph + co], all phases folded into N (kernel % stride == 0),
+//                t' over the (Jx,Jy,Jz) taps of the padded correlation
+//   CONVT_PHASE  wg[t][ci][co] of phase (px,py,pz), t over its (Jx,Jy,Jz) taps (plain layout)
+//   CONVT_DGRAD  wg[t][co][ci]   (co < UCs, ci < CinW)
 enum PrepKind { PREP_CONV_FWD = 0, PREP_CONV_DGRAD = 1, PREP_CONVT_FUSED = 2,
                 PREP_CONVT_PHASE = 3, PREP_CONVT_DGRAD = 4 };
 struct PrepJob {

@@ -1130,172 +1130,6 @@ int launch_from_cl(const float *xcl, float *x, int B, int C, int Cs, int64_t V, 
   return 0;
 }
 
-// ---------------------------------------------------------------------------
-// Effective (folded, block-diagonal) Conv3d weight element W_eff[o][e][t].
-__device__ inline float weff(const float *w, int o, int e, int t, int Cout, int Cin_g,
-                             int groups, int fold_mod, int T) {
-  const int g = o / (Cout / groups);
-  const int cin_total = groups * Cin_g;
-  float s = 0.f;
-  for (int cp = e; cp < cin_total; cp += fold_mod) {
-    const int c = cp - g * Cin_g;
-    if (c >= 0 && c < Cin_g) s += w[((size_t)o * Cin_g + c) * T + t];
-  }
-  return s;
-}
-
-__device__ __forceinline__ int64_t prep_count(const WPack &pk, int T, int ICs, int CoutW) {
-  return wpack_count(pk, T, ICs, CoutW);
-}
-// (t, ci, co) of element i of the prepared buffer (plain or packed layout).
-__device__ __forceinline__ bool prep_index(const WPack &pk, int64_t i, int T, int ICs, int CoutW,
-                                           int &t, int &ci, int &co) {
-  if (pk.on) return wpack_decode(pk, i, T, t, ci, co);
-  co = (int)(i % CoutW);
-  const int64_t q = i / CoutW;
-  ci = (int)(q % ICs);
-  t = (int)(q / ICs);
-  return true;
-}
-
-__global__ void __launch_bounds__(256)
-prep_conv_fwd_kernel(const float *w, float *wg, int Cout, int Cin_g, int groups,
-                     int fold_mod, int T, int ECs, int CoutW, int E, WPack pk) {
-  const int64_t n = prep_count(pk, T, ECs, CoutW);
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * 256) {
-    int t, e, co;
-    float v = 0.f;
-    if (prep_index(pk, i, T, ECs, CoutW, t, e, co) && co < Cout && e < E)
-      v = weff(w, co, e, t, Cout, Cin_g, groups, fold_mod, T);
-    wg[i] = v;
-  }
-}
-
-int launch_prep_conv_fwd(const float *w, float *wg, int Cout, int Cin_g, int groups,
-                         int fold_mod, int T, int ECs, int CoutW, WPack pk, hipStream_t s) {
-  const int E = std::min(fold_mod, groups * Cin_g);
-  const int64_t n = wpack_count(pk, T, ECs, CoutW);
-  HCU_TIMED(s, "prep_conv_fwd_kernel", 0.0, 0.0, HCU_LAUNCH(prep_conv_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, s, w, wg, Cout,
-                     Cin_g, groups, fold_mod, T, ECs, CoutW, E, pk));
-  HCU_CHECK_LAUNCH();
-  return 0;
-}
-
-// dgrad GEMM: rows (ci of the GEMM) = conv output channels co, cols = input channels e.
-__global__ void __launch_bounds__(256)
-prep_conv_dgrad_kernel(const float *w, float *wg, int Cout, int Cin_g, int groups,
-                       int fold_mod, int T, int OCs, int EW, int E, WPack pk) {
-  const int64_t n = prep_count(pk, T, OCs, EW);
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * 256) {
-    int tp, co, e;
-    float v = 0.f;
-    if (prep_index(pk, i, T, OCs, EW, tp, co, e) && co < Cout && e < E)
-      v = weff(w, co, e, T - 1 - tp, Cout, Cin_g, groups, fold_mod, T);
-    wg[i] = v;
-  }
-}
-
-int launch_prep_conv_dgrad(const float *w, float *wg, int Cout, int Cin_g, int groups,
-                           int fold_mod, int T, int OCs, int EW, int E, WPack pk, hipStream_t s) {
-  const int64_t n = wpack_count(pk, T, OCs, EW);
-  HCU_TIMED(s, "prep_conv_dgrad_kernel", 0.0, 0.0, HCU_LAUNCH(prep_conv_dgrad_kernel, dim3(grid_for(n)), dim3(256), 0, s, w, wg, Cout,
-                     Cin_g, groups, fold_mod, T, OCs, EW, E, pk));
-  HCU_CHECK_LAUNCH();
-  return 0;
-}
-
-__global__ void __launch_bounds__(256)
-prep_convt_fwd_kernel(const float *w, float *wg, int Cin, int Cout, int KX, int KY, int KZ,
-                      int sx, int sy, int sz, int px, int py, int pz, int Jx, int Jy,
-                      int Jz, int ICs, int CoutW) {
-  const int Tp = Jx * Jy * Jz;
-  const int64_t n = (int64_t)Tp * ICs * CoutW;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * 256) {
-    const int co = (int)(i % CoutW);
-    const int64_t q = i / CoutW;
-    const int ci = (int)(q % ICs);
-    const int t = (int)(q / ICs);
-    const int tz = t % Jz, ty = (t / Jz) % Jy, tx = t / (Jz * Jy);
-    const int kx = px + sx * (Jx - 1 - tx), ky = py + sy * (Jy - 1 - ty),
-              kz = pz + sz * (Jz - 1 - tz);
-    float v = 0.f;
-    if (ci < Cin && co < Cout && kx < KX && ky < KY && kz < KZ)
-      v = w[((((size_t)ci * Cout + co) * KX + kx) * KY + ky) * KZ + kz];
-    wg[i] = v;
-  }
-}
-
-int launch_prep_convt_fwd(const float *w, float *wg, int Cin, int Cout, int KX, int KY,
-                          int KZ, int sx, int sy, int sz, int px, int py, int pz, int Jx,
-                          int Jy, int Jz, int ICs, int CoutW, hipStream_t s) {
-  const int64_t n = (int64_t)Jx * Jy * Jz * ICs * CoutW;
-  HCU_TIMED(s, "prep_convt_fwd_kernel", 0.0, 0.0, HCU_LAUNCH(prep_convt_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, s, w, wg, Cin,
-                     Cout, KX, KY, KZ, sx, sy, sz, px, py, pz, Jx, Jy, Jz, ICs, CoutW));
-  HCU_CHECK_LAUNCH();
-  return 0;
-}
-
-__global__ void __launch_bounds__(256)
-prep_convt_fused_kernel(const float *w, float *wg, int Cin, int Cout, int KX, int KY, int KZ,
-                        int sx, int sy, int sz, int ICs, int CoutW, WPack pk) {
-  const int Jx = KX / sx, Jy = KY / sy, Jz = KZ / sz;
-  const int T = Jx * Jy * Jz;
-  const int nph = sx * sy * sz;
-  const int64_t n = prep_count(pk, T, ICs, CoutW);
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * 256) {
-    int t, ci, nn;
-    float v = 0.f;
-    if (prep_index(pk, i, T, ICs, CoutW, t, ci, nn) && ci < Cin && nn < nph * Cout) {
-      const int ph = nn / Cout, co = nn % Cout;
-      const int qz = ph % sz, qy = (ph / sz) % sy, qx = ph / (sz * sy);
-      const int tz = t % Jz, ty = (t / Jz) % Jy, tx = t / (Jz * Jy);
-      const int kx = qx + sx * (Jx - 1 - tx), ky = qy + sy * (Jy - 1 - ty),
-                kz = qz + sz * (Jz - 1 - tz);
-      v = w[((((size_t)ci * Cout + co) * KX + kx) * KY + ky) * KZ + kz];
-    }
-    wg[i] = v;
-  }
-}
-
-int launch_prep_convt_fused(const float *w, float *wg, int Cin, int Cout, int KX, int KY,
-                            int KZ, int sx, int sy, int sz, int ICs, int CoutW, WPack pk,
-                            hipStream_t s) {
-  const int T = (KX / sx) * (KY / sy) * (KZ / sz);
-  const int64_t n = wpack_count(pk, T, ICs, CoutW);
-  HCU_TIMED(s, "prep_convt_fused_kernel", 0.0, 0.0,
-            HCU_LAUNCH(prep_convt_fused_kernel, dim3(grid_for(n)), dim3(256), 0, s, w, wg,
-                               Cin, Cout, KX, KY, KZ, sx, sy, sz, ICs, CoutW, pk));
-  HCU_CHECK_LAUNCH();
-  return 0;
-}
-
-__global__ void __launch_bounds__(256)
-prep_convt_dgrad_kernel(const float *w, float *wg, int Cin, int Cout, int T, int UCs,
-                        int CinW, WPack pk) {
-  const int64_t n = prep_count(pk, T, UCs, CinW);
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * 256) {
-    int t, co, ci;
-    float v = 0.f;
-    if (prep_index(pk, i, T, UCs, CinW, t, co, ci) && ci < Cin && co < Cout)
-      v = w[((size_t)ci * Cout + co) * T + t];
-    wg[i] = v;
-  }
-}
-
-int launch_prep_convt_dgrad(const float *w, float *wg, int Cin, int Cout, int T, int UCs,
-                            int CinW, WPack pk, hipStream_t s) {
-  const int64_t n = wpack_count(pk, T, UCs, CinW);
-  HCU_TIMED(s, "prep_convt_dgrad_kernel", 0.0, 0.0, HCU_LAUNCH(prep_convt_dgrad_kernel, dim3(grid_for(n)), dim3(256), 0, s, w, wg, Cin,
-                     Cout, T, UCs, CinW, pk));
-  HCU_CHECK_LAUNCH();
-  return 0;
-}
-
 // out_conv weight/bias gradient from the fused backward's partial rows
 // (one workgroup per dw/db element).
 __global__ void __launch_bounds__(256)

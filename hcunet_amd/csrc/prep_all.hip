@@ -1,9 +1,9 @@
-// All weight re-layouts of one network step in a few launches (one workgroup
-// row per job) instead of one launch per layer: the executor prepares every
-// conv / convT weight once at the start of forward into the `saved`
-// workspace, and forward and backward read the prepared images from there.
-// Element i of a job is exactly what the per-layer prep_* kernel in
-// pointwise.hip writes for that layer (same index decoding, same values).
+// Every weight re-layout (PyTorch layout -> the GEMM images, PrepKind in
+// common.h), a few launches per network step (one workgroup row per job): the
+// executor prepares every conv / convT weight once at the start of forward
+// into `saved`, where forward and backward read the images; the per-op entry
+// points run a single job into their scratch.  Element i of a job is decoded
+// to its image's (tap, row, column) and evaluated from the weight; padding 0.
 #include "common.h"
 #include "timing.h"
 #include <algorithm>

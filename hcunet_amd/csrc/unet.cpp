@@ -24,6 +24,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -297,13 +298,26 @@ WGradJob conv_wgrad_job(const ConvLayer &L, const WGradArgs &w) {
                                wgrad_slab_acs(w)));
 }
 
-// Conv3d with stride / zero padding (nn.Conv3d(..., stride, padding), the
-// r_unet.py layers): out = floor((in + 2P - D(K-1) - 1) / S) + 1.  Forward:
-// o*S + t*D - P; input gradient (stride 1): the full correlation with padding
-// D(K-1) - P; weight gradient: A offset o*S + t*D - P.  A dilated kernel whose
-// halo does not fit the kernels' LDS runs on the dilation sub-lattices (s2b).
-int setup_conv_general(ConvLayer &L, const Dims &in, int Cout, int groups, int fold_mod,
-                       int cin_total, const char *name) {
+// Conv3d, optionally with stride / zero padding (nn.Conv3d(..., stride, padding),
+// the r_unet.py layers; null: stride 1, no padding -- the U-Net is valid):
+// out = floor((in + 2P - D(K-1) - 1) / S) + 1.  Forward: o*S + t*D - P; input
+// gradient (stride 1): the full correlation with padding D(K-1) - P; weight
+// gradient: A offset o*S + t*D - P.
+// sublattice (layer chains, the only executor of that form): a dilated kernel
+// whose halo does not fit the kernels' LDS may be planned on the dilation
+// sub-lattices (s2b), so every planner runs before an error is returned.
+// Without it the first planner's error is returned as it stands.
+int setup_conv(ConvLayer &L, const Dims &in, int Cout, int groups, int fold_mod, int cin_total,
+               const int K[3], const int D[3], const char *name, bool sublattice = false,
+               const int *S = nullptr, const int *P = nullptr) {
+  for (int i = 0; i < 3; ++i) {
+    L.K[i] = K[i];
+    L.D[i] = D[i];
+    L.S[i] = S ? S[i] : 1;
+    L.P[i] = P ? P[i] : 0;
+    if (K[i] < 1 || D[i] < 1) return fail(HCU_ERR_INVALID, std::string(name) + ": bad kernel/dilation");
+    if (L.S[i] < 1 || L.P[i] < 0) return fail(HCU_ERR_INVALID, std::string(name) + ": bad stride/padding");
+  }
   if (groups < 1 || cin_total % groups || Cout % groups)
     return fail(HCU_ERR_INVALID, std::string(name) + ": channels must be divisible by groups");
   L.Cout = Cout;
@@ -328,6 +342,7 @@ int setup_conv_general(ConvLayer &L, const Dims &in, int Cout, int groups, int f
   L.out = mkdims(in.B, o[0], o[1], o[2], Cout, in.es);
   const bool bf = in.es == 2;
   auto plan_c = [&](GConvArgs &a) { return bf ? plan_bconv(a, kTargetBlocks) : plan_conv_fp32(a, kTargetBlocks); };
+  auto plan_w = [&](WGradArgs &w) { return bf ? plan_bwgrad(w, kTargetBlocks) : plan_wgrad(w, kTargetBlocks); };
   L.has_dgrad = L.S[0] == 1 && L.S[1] == 1 && L.S[2] == 1;
   L.s2b = false;
   // direct form
@@ -336,6 +351,7 @@ int setup_conv_general(ConvLayer &L, const Dims &in, int Cout, int groups, int f
     f.sx = L.S[0]; f.sy = L.S[1]; f.sz = L.S[2];
     f.px = L.P[0]; f.py = L.P[1]; f.pz = L.P[2];
     const int ef = plan_c(f);
+    if (ef && !sublattice) return ef;
     int ed = 0;
     GConvArgs dg{};
     if (L.has_dgrad) {
@@ -346,18 +362,19 @@ int setup_conv_general(ConvLayer &L, const Dims &in, int Cout, int groups, int f
       if (dg.px < 0 || dg.py < 0 || dg.pz < 0)
         return fail(HCU_ERR_UNSUPPORTED, std::string(name) + ": padding larger than dilation*(kernel-1)");
       ed = plan_c(dg);
+      if (ed && !sublattice) return ed;
     }
     WGradArgs w = wgrad_conv(in, L.out, L.K, L.D);
     w.asx = L.S[0]; w.asy = L.S[1]; w.asz = L.S[2];
     w.apx = L.P[0]; w.apy = L.P[1]; w.apz = L.P[2];
     compact_slab(w, L, bf);
-    const int ew = bf ? plan_bwgrad(w, kTargetBlocks) : plan_wgrad(w, kTargetBlocks);
+    const int ew = plan_w(w);
     const bool dil = L.D[0] > 1 || L.D[1] > 1 || L.D[2] > 1;
     if (!ef && !ed && !ew) {
       L.fwd = f;
       L.dgrad = dg;
       L.wg = conv_wgrad_job(L, w);
-    } else if (!dil || !L.has_dgrad) {
+    } else if (!sublattice || !dil || !L.has_dgrad) {
       return ef ? ef : ed ? ed : ew;
     } else {
       L.s2b = true;
@@ -395,7 +412,7 @@ int setup_conv_general(ConvLayer &L, const Dims &in, int Cout, int groups, int f
     WGradArgs w = wgrad_conv(L.sub_in, L.sub_out, L.K, one);
     w.apx = Pd[0]; w.apy = Pd[1]; w.apz = Pd[2];
     compact_slab(w, L, bf);
-    if (int e = bf ? plan_bwgrad(w, kTargetBlocks) : plan_wgrad(w, kTargetBlocks)) return e;
+    if (int e = plan_w(w)) return e;
     L.wg = conv_wgrad_job(L, w);
   }
   L.bn.C = Cout;
@@ -404,53 +421,6 @@ int setup_conv_general(ConvLayer &L, const Dims &in, int Cout, int groups, int f
   set_pw(L, in, cin_total);
   return 0;
 }
-
-int setup_conv(ConvLayer &L, const Dims &in, int Cout, int groups, int fold_mod, int cin_total,
-               const int K[3], const int D[3], const char *name, const int *S = nullptr,
-               const int *P = nullptr) {
-  for (int i = 0; i < 3; ++i) {
-    L.K[i] = K[i];
-    L.D[i] = D[i];
-    L.S[i] = S ? S[i] : 1;
-    L.P[i] = P ? P[i] : 0;
-    if (K[i] < 1 || D[i] < 1) return fail(HCU_ERR_INVALID, std::string(name) + ": bad kernel/dilation");
-    if (L.S[i] < 1 || L.P[i] < 0) return fail(HCU_ERR_INVALID, std::string(name) + ": bad stride/padding");
-  }
-  if (S || P) return setup_conv_general(L, in, Cout, groups, fold_mod, cin_total, name);
-  if (groups < 1 || cin_total % groups || Cout % groups)
-    return fail(HCU_ERR_INVALID, std::string(name) + ": channels must be divisible by groups");
-  L.Cout = Cout;
-  L.groups = groups;
-  L.Cin_g = cin_total / groups;
-  L.fold_mod = fold_mod;
-  L.E = std::min(fold_mod, cin_total);
-  set_parts(L, in);
-  L.T = K[0] * K[1] * K[2];
-  L.in = in;
-  const int ox = in.X - D[0] * (K[0] - 1), oy = in.Y - D[1] * (K[1] - 1), oz = in.Z - D[2] * (K[2] - 1);
-  if (ox < 1 || oy < 1 || oz < 1)
-    return fail(HCU_ERR_SHAPE, std::string(name) + ": Calculated padded input size per channel: (" +
-                                   std::to_string(in.X) + " x " + std::to_string(in.Y) + " x " +
-                                   std::to_string(in.Z) +
-                                   "). Kernel size can't be greater than actual input size");
-  L.out = mkdims(in.B, ox, oy, oz, Cout, in.es);
-  const bool bf = in.es == 2;
-  L.fwd = gconv_conv_fwd(in, L.out, K, D, Cout);
-  if (int e = bf ? plan_bconv(L.fwd, kTargetBlocks) : plan_conv_fp32(L.fwd, kTargetBlocks)) return e;
-  L.dgrad = gconv_conv_dgrad(in, L.out, K, D, L.E);
-  if (int e = bf ? plan_bconv(L.dgrad, kTargetBlocks) : plan_conv_fp32(L.dgrad, kTargetBlocks))
-    return e;
-  WGradArgs w = wgrad_conv(in, L.out, K, D);
-  compact_slab(w, L, bf);
-  if (int e = bf ? plan_bwgrad(w, kTargetBlocks) : plan_wgrad(w, kTargetBlocks)) return e;
-  L.wg = conv_wgrad_job(L, w);
-  L.bn.C = Cout;
-  L.bn.Cs = L.out.Cs;
-  L.bn.count = (double)L.out.vox();
-  set_pw(L, in, cin_total);
-  return 0;
-}
-
 
 // pad (layer chains; null: none): ConvTranspose3d padding, the crop of the full
 // output.  The forward writes the full output (into scratch) and crops it;
@@ -780,52 +750,73 @@ void track_conv(hcu_unet_plan &p, const ConvLayer &L) {
   p.need.rows((size_t)bwd_rows(L.out.vox(), L.out.Cs) * L.out.Cs * 2);
 }
 
-// Prepared (GEMM-layout) weights of every layer: written once per forward by
-// one batched launch, read by the forward and backward GEMMs.
-void add_prep(hcu_unet_plan &p, Region &saved, int kind, size_t n, int64_t src, const WPack &pk,
-              const int *prm, int np, size_t &off) {
+// The re-layout job (prep_all.hip) of the weight image the planned GEMM `a`
+// reads, with the kind's parameters (PrepJob::p).  src / dst stay 0: the
+// weight and the image themselves (the per-op entry points); add_prep places
+// a plan's jobs in the parameter buffer and in `saved`.
+PrepJob prep_job(int kind, const GConvArgs &a, std::initializer_list<int> prm) {
   PrepJob j{};
   j.kind = kind;
-  j.bf16 = p.es == 2;
-  j.n = (int64_t)n;
+  j.bf16 = (a.use_bconv && a.bes != 4) ? 1 : 0;   // (every convolution of a bf16 plan)
+  j.n = (int64_t)prep_elems(a);
+  j.pk = wpack_of(a);
+  std::copy(prm.begin(), prm.end(), j.p);
+  return j;
+}
+
+// A Conv3d layer's forward image (t, e, co) / input-gradient image (t', co, e).
+PrepJob conv_fwd_job(const ConvLayer &cl) {
+  return prep_job(PREP_CONV_FWD, cl.fwd,
+                  {cl.Cout, cl.Cin_g, cl.groups, cl.fold_mod, cl.T, cl.fwd.ICs, cl.fwd.CoutW,
+                   cl.part_c ? cl.fwd.ICs : std::min(cl.fold_mod, cl.groups * cl.Cin_g), cl.part_c, cl.part_cs});
+}
+PrepJob conv_dgrad_job(const ConvLayer &cl) {
+  return prep_job(PREP_CONV_DGRAD, cl.dgrad,
+                  {cl.Cout, cl.Cin_g, cl.groups, cl.fold_mod, cl.T, cl.dgrad.ICs, cl.dgrad.CoutW, cl.E,
+                   cl.part_c, cl.part_cs});
+}
+// A ConvTranspose3d layer's images: the phase-folded forward, one forward
+// phase (the plain [t][ci][co] layout of gconv) and the input gradient.
+PrepJob convt_fused_job(const ConvTLayer &u) {
+  return prep_job(PREP_CONVT_FUSED, u.fwdf,
+                  {u.Cin, u.Cout, u.K[0], u.K[1], u.K[2], u.S[0], u.S[1], u.S[2], u.fwdf.ICs, u.fwdf.CoutW,
+                   u.fwdf.cph});
+}
+PrepJob convt_phase_job(const ConvTLayer &u, size_t ph) {
+  const int *pj = &u.pJ[ph * 6];
+  const GConvArgs &a = u.phases[ph];
+  return prep_job(PREP_CONVT_PHASE, a,
+                  {u.Cin, u.Cout, u.K[0], u.K[1], u.K[2], u.S[0], u.S[1], u.S[2], pj[0], pj[1], pj[2], pj[3],
+                   pj[4], pj[5], a.ICs, a.CoutW});
+}
+PrepJob convt_dgrad_job(const ConvTLayer &u) {
+  return prep_job(PREP_CONVT_DGRAD, u.dgrad, {u.Cin, u.Cout, u.T, u.dgrad.ICs, u.dgrad.CoutW});
+}
+
+// Prepared (GEMM-layout) weights of every layer: written once per forward by
+// one batched launch, read by the forward and backward GEMMs.  Places job `j`
+// of the weight at parameter offset `src`; off: its image in `saved`.
+void add_prep(hcu_unet_plan &p, Region &saved, PrepJob j, int64_t src, size_t &off) {
   j.src = src;
-  off = saved.take_floats(j.bf16 ? (n + 1) / 2 : n);
+  off = saved.take_floats(j.bf16 ? ((size_t)j.n + 1) / 2 : (size_t)j.n);
   j.dst = (int64_t)(off / sizeof(float));
-  j.pk = pk;
-  std::copy(prm, prm + np, j.p);
   p.prep_jobs.push_back(j);
 }
 
 void conv_prep(hcu_unet_plan &p, Region &saved, ConvLayer &cl) {
-  const int pf[10] = {cl.Cout, cl.Cin_g, cl.groups, cl.fold_mod, cl.T, cl.fwd.ICs, cl.fwd.CoutW,
-                      cl.part_c ? cl.fwd.ICs : std::min(cl.fold_mod, cl.groups * cl.Cin_g),
-                      cl.part_c, cl.part_cs};
-  add_prep(p, saved, PREP_CONV_FWD, prep_elems(cl.fwd), cl.w_off, wpack_of(cl.fwd), pf, 10, cl.wf_off);
-  if (!cl.has_dgrad) return;
-  const int pd[10] = {cl.Cout, cl.Cin_g, cl.groups, cl.fold_mod, cl.T, cl.dgrad.ICs, cl.dgrad.CoutW,
-                      cl.E, cl.part_c, cl.part_cs};
-  add_prep(p, saved, PREP_CONV_DGRAD, prep_elems(cl.dgrad), cl.w_off, wpack_of(cl.dgrad), pd, 10,
-           cl.wd_off);
+  add_prep(p, saved, conv_fwd_job(cl), cl.w_off, cl.wf_off);
+  if (cl.has_dgrad) add_prep(p, saved, conv_dgrad_job(cl), cl.w_off, cl.wd_off);
 }
 
 void convt_prep(hcu_unet_plan &p, Region &saved, ConvTLayer &u) {
   if (u.fused) {
-    const int pf[11] = {u.Cin, u.Cout, u.K[0], u.K[1], u.K[2], u.S[0], u.S[1], u.S[2],
-                        u.fwdf.ICs, u.fwdf.CoutW, u.fwdf.cph};
-    add_prep(p, saved, PREP_CONVT_FUSED, prep_elems(u.fwdf), u.w_off, wpack_of(u.fwdf), pf, 11, u.wf_off);
+    add_prep(p, saved, convt_fused_job(u), u.w_off, u.wf_off);
   } else {
     u.wph_off.assign(u.phases.size(), 0);
-    for (size_t ph = 0; ph < u.phases.size(); ++ph) {
-      const int *pj = &u.pJ[ph * 6];
-      const GConvArgs &a = u.phases[ph];
-      const int pf[16] = {u.Cin, u.Cout, u.K[0], u.K[1], u.K[2], u.S[0], u.S[1], u.S[2],
-                          pj[0], pj[1], pj[2], pj[3], pj[4], pj[5], a.ICs, a.CoutW};
-      add_prep(p, saved, PREP_CONVT_PHASE, (size_t)pj[3] * pj[4] * pj[5] * a.ICs * a.CoutW, u.w_off,
-               WPack{}, pf, 16, u.wph_off[ph]);
-    }
+    for (size_t ph = 0; ph < u.phases.size(); ++ph)
+      add_prep(p, saved, convt_phase_job(u, ph), u.w_off, u.wph_off[ph]);
   }
-  const int pd[5] = {u.Cin, u.Cout, u.T, u.dgrad.ICs, u.dgrad.CoutW};
-  add_prep(p, saved, PREP_CONVT_DGRAD, prep_elems(u.dgrad), u.w_off, wpack_of(u.dgrad), pd, 5, u.wd_off);
+  add_prep(p, saved, convt_dgrad_job(u), u.w_off, u.wd_off);
 }
 
 // The forward's images / the input-gradient images only the backward reads.
@@ -1089,7 +1080,19 @@ struct Ctx {
   // saved workspace, or a layer chain's caller-owned image buffer
   // (hcu_chain_forward_images), which then starts at plan offset img_lo.
   char *wi = nullptr;
+  // split: the branch runs on the plan's side stream; images: a layer chain's
+  // caller-owned weight-image buffer (null: the images are in `saved`)
+  Ctx(const hcu_unet_plan &plan, const hcu_unet_tensors &tensors, hipStream_t stream, bool split_ = false,
+      void *images = nullptr)
+      : p(plan), t(tensors), s(stream), sv((char *)tensors.saved), sc((char *)tensors.scratch),
+        P(tensors.params), G(tensors.grads), ws(split_ ? plan.side : stream), split(split_),
+        wi(images ? (char *)images - plan.img_lo : nullptr) {}
   char *wimg() const { return wi ? wi : sv; }
+  float *image(size_t off) const { return fptr(wimg(), off); }
+  // A parameter / its gradient at a plan offset; null for an absent one
+  // (offset < 0: a chain layer without bias)
+  const float *param(int64_t off) const { return off >= 0 ? P + off : nullptr; }
+  float *grad(int64_t off) const { return off >= 0 ? G + off : nullptr; }
   int bf() const { return p.es == 2; }   // bf16 activation storage
   float *part() const { return fptr(sc, p.part_off); }
   // Weight-gradient slab arena: each layer's partial slabs stay until its
@@ -1199,6 +1202,63 @@ void tag(const std::string &layer, const char *phase) {
   if (timing_on()) timing_set_tag((layer + "." + phase).c_str());
 }
 
+// The planned convolution `plan` bound to its operands: the input (with the
+// BatchNorm scale / shift its staging applies, or null), the weight image, the
+// bias, the output, the epilogue's statistics rows (or null) and the K-split
+// partials (kernels that do not split ignore them).
+GConvArgs bind_conv(const GConvArgs &plan, const float *in, const float *in_scale, const float *in_shift,
+                    const float *w, const float *bias, float *out, float *stats, float *partial) {
+  GConvArgs a = plan;
+  a.in = in;
+  a.in_scale = in_scale;
+  a.in_shift = in_shift;
+  a.w = w;
+  a.bias = bias;
+  a.out = out;
+  a.stats = stats;
+  a.partial = partial;
+  return a;
+}
+
+// Binds and launches (the sites without a fused BatchNorm backward, fuse_bnbwd).
+int run_conv(const GConvArgs &plan, const float *in, const float *in_scale, const float *in_shift,
+             const float *w, const float *bias, float *out, float *stats, float *partial, hipStream_t s) {
+  return launch_conv_any(bind_conv(plan, in, in_scale, in_shift, w, bias, out, stats, partial), s);
+}
+
+// ConvTranspose3d forward of `u` into U, its full output (a chain crops a
+// padded layer's afterwards): the phase-folded GEMM, else one launch per phase.
+int convt_forward(const Ctx &c, const ConvTLayer &u, const float *in, const float *in_scale,
+                  const float *in_shift, float *U) {
+  const float *bias = c.param(u.b_off);
+  if (u.fused)
+    return run_conv(u.fwdf, in, in_scale, in_shift, c.image(u.wf_off), bias, U, nullptr, c.kpart(), c.s);
+  for (size_t ph = 0; ph < u.phases.size(); ++ph)
+    if (int e = run_conv(u.phases[ph], in, in_scale, in_shift, c.image(u.wph_off[ph]), bias, U, nullptr,
+                         c.kpart(), c.s))
+      return e;
+  return 0;
+}
+
+// The pointwise kernel (pwconv.hip) of the 1x1x1 layer L: its forward (in = x,
+// out = y) or its input gradient (in = dy, out = dx; no bias).
+PwArgs pw_args(const ConvLayer &L, bool dgrad, const float *in, const float *w, const float *bias, float *out) {
+  PwArgs a{};
+  a.in = reinterpret_cast<const uint16_t *>(in);
+  a.w = w;
+  a.bias = dgrad ? nullptr : bias;
+  a.out = reinterpret_cast<uint16_t *>(out);
+  a.nvox = L.out.vox();
+  a.ICs = dgrad ? L.out.Cs : L.in.Cs;
+  a.OCs = dgrad ? L.in.Cs : L.out.Cs;
+  a.Cin = L.Cin_g;
+  a.Cout = L.Cout;
+  a.part_c = L.part_c;
+  a.part_cs = L.part_cs;
+  a.dgrad = dgrad ? 1 : 0;
+  return a;
+}
+
 // in_fmt > 0 (the first layer, hcu_unet_plan::ncx_first): `in` is the
 // caller's NCXYZ input volume, read by the conv's own halo staging, which also
 // writes the channels-last copy xcl_out (when not null).
@@ -1206,19 +1266,12 @@ int conv_forward(const Ctx &c, const ConvLayer &L, const float *in, const float 
                  const float *ish, int training, int in_fmt = 0, float *xcl_out = nullptr) {
   HCU_HIP(hipGetLastError());
   tag(L.name, "fwd");
-  GConvArgs a = L.fwd;
-  a.in = in;
+  // (in_fmt: the weight is read in the PyTorch layout by the NCXYZ staging)
+  GConvArgs a = bind_conv(L.fwd, in, isc, ish, in_fmt ? c.P + L.w_off : c.image(L.wf_off), c.param(L.b_off),
+                          c.fptr(c.sv, L.y_off), training ? c.part() : nullptr, c.kpart());
   a.in_fmt = in_fmt;
   a.in_c = in_fmt ? L.in.C : 0;
   a.xcl = xcl_out;
-  if (in_fmt) a.w = c.P + L.w_off;   // (read in the PyTorch layout by the NCXYZ staging)
-  a.in_scale = isc;
-  a.in_shift = ish;
-  if (!in_fmt) a.w = c.fptr(c.wimg(), L.wf_off);
-  a.bias = L.b_off >= 0 ? c.P + L.b_off : nullptr;
-  a.out = c.fptr(c.sv, L.y_off);
-  a.stats = training ? c.part() : nullptr;
-  a.partial = c.kpart();
   const BNCoef coef = coef_at(c.sv, L.bn);
   if (int e = launch_conv_any(a, c.s)) return e;
   return launch_bn_fwd_finalize(c.part(), gconv_rows(L.fwd), L.fwd.CoutW, L.bn.C, L.bn.Cs,
@@ -1257,6 +1310,20 @@ int finish_bn(const Ctx &c, const ConvLayer &bnl, int R, int W, float *dz, int t
 int finish_bnbwd(const Ctx &c, const GConvArgs &a, const ConvLayer &bnl, float *dz, int training,
                  int accumulate) {
   return finish_bn(c, bnl, gconv_rows(a), a.CoutW, dz, training, accumulate);
+}
+
+// Input gradient dP of the ConvTranspose3d `u` from dU.  With `bnl`, the
+// layer that produced u's input, its BatchNorm+ReLU backward is fused into the
+// kernel where the planned one can (fuse_bnbwd): dP then leaves as bnl's
+// d(pre-BN y).  fused: whether that happened (else the caller's to run).
+int convt_dgrad(Ctx &c, const ConvTLayer &u, const float *dU, float *dP, const ConvLayer *bnl, int training,
+                int accumulate, bool &fused) {
+  GConvArgs a = bind_conv(u.dgrad, dU, nullptr, nullptr, c.image(u.wd_off), nullptr, dP, nullptr, c.kpart());
+  fused = fuse_bnbwd(c, a, bnl);
+  if (int e = launch_conv_any(a, c.s)) return e;
+  if (!fused) return 0;
+  tag(bnl->name, "bnbwd");
+  return finish_bnbwd(c, a, *bnl, dP, training, accumulate);
 }
 
 // Weight/bias gradient and (optionally) input gradient of one Conv3d layer.
@@ -1322,8 +1389,7 @@ int conv_wgrad(Ctx &c, const ConvLayer &L, const float *A, const float *asc, con
                const float *dy, int dy_slot, int accumulate) {
   tag(L.name, "wgrad");
   if (int e = c.fork()) return e;
-  if (int e = run_wgrad(c, L.wg, A, asc, ash, dy, c.G + L.w_off, L.b_off >= 0 ? c.G + L.b_off : nullptr,
-                        accumulate))
+  if (int e = run_wgrad(c, L.wg, A, asc, ash, dy, c.G + L.w_off, c.grad(L.b_off), accumulate))
     return e;
   return c.read_done(dy_slot);
 }
@@ -1339,29 +1405,13 @@ int conv_backward(Ctx &c, const ConvLayer &L, const float *A, const float *asc,
   if (!dA) return 0;
   tag(L.name, "dgrad");
   if (L.pw && !bnl && !colsum) {   // (the chains' non-BatchNorm 1x1x1 convolutions)
-    PwArgs w{};
-    w.in = reinterpret_cast<const uint16_t *>(dy);
-    w.w = c.P + L.w_off;
-    w.out = reinterpret_cast<uint16_t *>(dA);
-    w.nvox = L.out.vox();
-    w.ICs = L.out.Cs;
-    w.OCs = L.in.Cs;
-    w.Cin = L.Cin_g;
-    w.Cout = L.Cout;
-    w.part_c = L.part_c;
-    w.part_cs = L.part_cs;
-    w.dgrad = 1;
-    if (int e = launch_pw(w, c.s)) return e;
+    if (int e = launch_pw(pw_args(L, true, dy, c.P + L.w_off, nullptr, dA), c.s)) return e;
     // (wg_late is not reached here today: its one caller, the U-Net's level-0 conv2, passes bnl)
     return wg_late ? conv_wgrad(c, L, A, asc, ash, dy, dy_slot, accumulate) : 0;
   }
-  GConvArgs a = L.dgrad;
-  a.in = dy;
-  a.w = c.fptr(c.wimg(), L.wd_off);
-  a.out = dA;
-  a.partial = c.kpart();
+  // (statistics rows: colsum, unless the fused BatchNorm backward takes them)
+  GConvArgs a = bind_conv(L.dgrad, dy, nullptr, nullptr, c.image(L.wd_off), nullptr, dA, colsum, c.kpart());
   const bool fused = fuse_bnbwd(c, a, bnl);
-  if (!fused && colsum) a.stats = colsum;
   if (int e = launch_conv_any(a, c.s)) return e;
   if (wg_late)
     if (int e = conv_wgrad(c, L, A, asc, ash, dy, dy_slot, accumulate)) return e;
@@ -1606,9 +1656,7 @@ bool side_enabled();
 // tensor every step (a data loader) does not key a new graph.
 static int enqueue_forward(const hcu_unet_plan &p, const hcu_unet_tensors *t, int training,
                            hipStream_t stream, int part = 0, bool split = false) {
-  Ctx c{p, *t, (hipStream_t)stream, (char *)t->saved, (char *)t->scratch, t->params, t->grads};
-  c.split = split;
-  c.ws = split ? p.side : c.s;
+  Ctx c(p, *t, stream, split);
   const hcu_unet_spec &s = p.spec;
   float *xcl = c.fptr(c.sv, p.xcl_off);
   if (part != 2) {
@@ -1689,29 +1737,7 @@ static int enqueue_forward(const hcu_unet_plan &p, const hcu_unet_tensors *t, in
     const ConvTLayer &u = p.up[j];
     tag(u.name, "fwd");
     float *U = c.fptr(c.sv, u.u_off);
-    if (u.fused) {
-      GConvArgs a = u.fwdf;
-      a.in = src;
-      a.in_scale = ssc;
-      a.in_shift = ssh;
-      a.w = c.fptr(c.wimg(), u.wf_off);
-      a.bias = c.P + u.b_off;
-      a.out = U;
-      a.stats = nullptr;
-      a.partial = c.kpart();
-      if (int e = launch_conv_any(a, c.s)) return e;
-    }
-    for (size_t ph = 0; !u.fused && ph < u.phases.size(); ++ph) {
-      GConvArgs a = u.phases[ph];
-      a.in = src;
-      a.in_scale = ssc;
-      a.in_shift = ssh;
-      a.w = c.fptr(c.wimg(), u.wph_off[ph]);
-      a.bias = c.P + u.b_off;
-      a.out = U;
-      a.stats = nullptr;
-      if (int e = launch_gconv(a, c.s)) return e;
-    }
+    if (int e = convt_forward(c, u, src, ssc, ssh, U)) return e;
     const ConvLayer &c1 = p.uc1[j], &c2 = p.uc2[j];
     if (int e = conv_forward(c, c1, U, nullptr, nullptr, training)) return e;
     const BNCoef b1 = coef_at(c.sv, c1.bn);
@@ -1800,9 +1826,7 @@ static int enqueue_backward(const hcu_unet_plan &p, const hcu_unet_tensors *t, c
                             float *dx, int training, int accumulate, hipStream_t stream,
                             bool split, bool record_grad_events) {
   const hcu_unet_spec &s = p.spec;
-  Ctx c{p, *t, (hipStream_t)stream, (char *)t->saved, (char *)t->scratch, t->params, t->grads};
-  c.split = split;
-  c.ws = split ? p.side : c.s;
+  Ctx c(p, *t, stream, split);
   c.arm_chain();
   // an eval-mode forward prepared only the forward weight images: the
   // input-gradient images are laid out here
@@ -1872,22 +1896,10 @@ static int enqueue_backward(const hcu_unet_plan &p, const hcu_unet_tensors *t, c
     if (int e = c.read_done(su)) return e;
     tag(u.name, "dgrad");
     if (int e = c.alloc(sd)) return e;
-    {
-      float *dP = c.buf(sd);
-      GConvArgs a = u.dgrad;
-      a.in = dU;
-      a.w = c.fptr(c.wimg(), u.wd_off);
-      a.out = dP;
-      a.partial = c.kpart();
-      const bool fused = fuse_bnbwd(c, a, &prev);
-      if (int e = launch_conv_any(a, c.s)) return e;
-      if (fused) {
-        tag(prev.name, "bnbwd");
-        if (int e = finish_bnbwd(c, a, prev, dP, training, accumulate)) return e;
-      } else if (int e = bn_backward(c, prev, dP, nullptr, nullptr, training, accumulate)) {
-        return e;
-      }
-    }
+    bool fused = false;
+    if (int e = convt_dgrad(c, u, dU, c.buf(sd), &prev, training, accumulate, fused)) return e;
+    if (!fused)
+      if (int e = bn_backward(c, prev, c.buf(sd), nullptr, nullptr, training, accumulate)) return e;
     cur = sd;
   }
   // Data-parallel overlap: every gradient of a finished group is written by
@@ -2051,17 +2063,9 @@ int make_op(const hcu_conv_desc *d, OpPlan &op) {
   return 0;
 }
 
-// One weight re-layout through the batched prep kernel (the bf16 images).
-int prep_one(int kind, const GConvArgs &a, const int *prm, int np, const float *w, float *dst,
-             hipStream_t s) {
-  PrepJob j{};
-  j.kind = kind;
-  j.bf16 = (a.use_bconv && a.bes != 4) ? 1 : 0;
-  j.n = (int64_t)prep_elems(a);
-  j.src = 0;
-  j.dst = 0;
-  j.pk = wpack_of(a);
-  std::copy(prm, prm + np, j.p);
+// One layer's weight re-layout (a plan's job record, prep_job) from the weight
+// `w` into the image `dst`.
+int prep_one(const PrepJob &j, const float *w, float *dst, hipStream_t s) {
   return launch_prep_all(w, dst, &j, 1, s);
 }
 
@@ -2100,54 +2104,18 @@ int hcu_conv_fwd_cl(const hcu_conv_desc *d, const float *x, const float *w, cons
   float *wprep = reinterpret_cast<float *>((char *)scratch + op.wprep_off);
   float *kpart = reinterpret_cast<float *>((char *)scratch + op.kpart_off);
   if (!d->transposed) {
-    const ConvLayer &L = op.conv;
-    if (L.fwd.use_bconv) {
-      const int pf[8] = {L.Cout, L.Cin_g, L.groups, L.fold_mod, L.T, L.fwd.ICs, L.fwd.CoutW,
-                         std::min(L.fold_mod, L.groups * L.Cin_g)};
-      if (int e = prep_one(PREP_CONV_FWD, L.fwd, pf, 8, w, wprep, s)) return e;
-    } else if (int e = launch_prep_conv_fwd(w, wprep, L.Cout, L.Cin_g, L.groups, L.fold_mod, L.T,
-                                            L.fwd.ICs, L.fwd.CoutW, wpack_of(L.fwd), s)) {
-      return e;
-    }
-    GConvArgs a = L.fwd;
-    a.in = x;
-    a.w = wprep;
-    a.bias = bias;
-    a.out = y;
-    a.partial = kpart;
-    return launch_conv_any(a, s);
+    if (int e = prep_one(conv_fwd_job(op.conv), w, wprep, s)) return e;
+    return run_conv(op.conv.fwd, x, nullptr, nullptr, wprep, bias, y, nullptr, kpart, s);
   }
   const ConvTLayer &u = op.ct;
   if (u.fused) {
-    GConvArgs a = u.fwdf;
-    if (a.use_bconv) {
-      const int pf[11] = {u.Cin, u.Cout, u.K[0], u.K[1], u.K[2], u.S[0], u.S[1], u.S[2], a.ICs,
-                          a.CoutW, a.cph};
-      if (int e = prep_one(PREP_CONVT_FUSED, a, pf, 11, w, wprep, s)) return e;
-    } else if (int e = launch_prep_convt_fused(w, wprep, u.Cin, u.Cout, u.K[0], u.K[1], u.K[2],
-                                               u.S[0], u.S[1], u.S[2], a.ICs, a.CoutW,
-                                               wpack_of(a), s)) {
-      return e;
-    }
-    a.in = x;
-    a.w = wprep;
-    a.bias = bias;
-    a.out = y;
-    a.partial = kpart;
-    return launch_conv_any(a, s);
+    if (int e = prep_one(convt_fused_job(u), w, wprep, s)) return e;
+    return run_conv(u.fwdf, x, nullptr, nullptr, wprep, bias, y, nullptr, kpart, s);
   }
+  // (every phase's image goes through the one scratch buffer, just ahead of its launch)
   for (size_t ph = 0; ph < u.phases.size(); ++ph) {
-    const int *pj = &u.pJ[ph * 6];
-    GConvArgs a = u.phases[ph];
-    if (int e = launch_prep_convt_fwd(w, wprep, u.Cin, u.Cout, u.K[0], u.K[1], u.K[2], u.S[0],
-                                      u.S[1], u.S[2], pj[0], pj[1], pj[2], pj[3], pj[4], pj[5],
-                                      a.ICs, a.CoutW, s))
-      return e;
-    a.in = x;
-    a.w = wprep;
-    a.bias = bias;
-    a.out = y;
-    if (int e = launch_gconv(a, s)) return e;
+    if (int e = prep_one(convt_phase_job(u, ph), w, wprep, s)) return e;
+    if (int e = run_conv(u.phases[ph], x, nullptr, nullptr, wprep, bias, y, nullptr, kpart, s)) return e;
   }
   return HCU_OK;
 }
@@ -2160,35 +2128,9 @@ int hcu_conv_dgrad_cl(const hcu_conv_desc *d, const float *dy, const float *w, f
   hipStream_t s = (hipStream_t)stream;
   float *wprep = reinterpret_cast<float *>((char *)scratch + op.wprep_off);
   float *kpart = reinterpret_cast<float *>((char *)scratch + op.kpart_off);
-  GConvArgs a;
-  if (!d->transposed) {
-    const ConvLayer &L = op.conv;
-    if (L.dgrad.use_bconv) {
-      const int pd[8] = {L.Cout, L.Cin_g, L.groups, L.fold_mod, L.T, L.dgrad.ICs, L.dgrad.CoutW,
-                         L.E};
-      if (int e = prep_one(PREP_CONV_DGRAD, L.dgrad, pd, 8, w, wprep, s)) return e;
-    } else if (int e = launch_prep_conv_dgrad(w, wprep, L.Cout, L.Cin_g, L.groups, L.fold_mod,
-                                              L.T, L.dgrad.ICs, L.dgrad.CoutW, L.E,
-                                              wpack_of(L.dgrad), s)) {
-      return e;
-    }
-    a = L.dgrad;
-  } else {
-    const ConvTLayer &u = op.ct;
-    if (u.dgrad.use_bconv) {
-      const int pd[5] = {u.Cin, u.Cout, u.T, u.dgrad.ICs, u.dgrad.CoutW};
-      if (int e = prep_one(PREP_CONVT_DGRAD, u.dgrad, pd, 5, w, wprep, s)) return e;
-    } else if (int e = launch_prep_convt_dgrad(w, wprep, u.Cin, u.Cout, u.T, u.dgrad.ICs,
-                                               u.dgrad.CoutW, wpack_of(u.dgrad), s)) {
-      return e;
-    }
-    a = u.dgrad;
-  }
-  a.in = dy;
-  a.w = wprep;
-  a.out = dx;
-  a.partial = kpart;
-  return launch_conv_any(a, s);
+  if (int e = prep_one(d->transposed ? convt_dgrad_job(op.ct) : conv_dgrad_job(op.conv), w, wprep, s)) return e;
+  return run_conv(d->transposed ? op.ct.dgrad : op.conv.dgrad, dy, nullptr, nullptr, wprep, nullptr, dx, nullptr,
+                  kpart, s);
 }
 
 int hcu_conv_wgrad_cl(const hcu_conv_desc *d, const float *x, const float *dy, float *dw,
@@ -2329,7 +2271,7 @@ int build_chain(hcu_unet_plan &p, const hcu_chain_spec &cs) {
       ConvLayer &L = o.conv;
       L.name = nm;
       if (int e = setup_conv(L, cur, s.out_channels, s.groups, fold_mod, cin_total, s.k, s.dil, "Conv3d",
-                             s.stride, s.pad))
+                             true, s.stride, s.pad))
         return e;
       if (L.s2b && o.bn_relu)
         return fail(HCU_ERR_UNSUPPORTED, "chain: BatchNorm after a sub-lattice (large dilated) Conv3d");
@@ -2452,8 +2394,7 @@ std::vector<ChainAct> chain_inputs(const hcu_unet_plan &p, char *sv, const void 
 // parameters, 2 = also the input-gradient ones (no re-layout then).
 int enqueue_chain_forward(const hcu_unet_plan &p, const hcu_unet_tensors *t, int training, hipStream_t s,
                           void *images = nullptr, int images_current = 0) {
-  Ctx c{p, *t, s, (char *)t->saved, (char *)t->scratch, t->params, t->grads};
-  if (images) c.wi = (char *)images - p.img_lo;
+  Ctx c(p, *t, s, false, images);
   const int es = p.es, bf = c.bf();
   tag(std::string("chain"), "fwd");
   if (!p.in_cl)
@@ -2478,45 +2419,20 @@ int enqueue_chain_forward(const hcu_unet_plan &p, const hcu_unet_tensors *t, int
         tag(L.name, "fwd");
         if (int e = launch_s2b(a.x, a.sc, a.sh, xs, p.B, L.in.X, L.in.Y, L.in.Z, L.in.Cs, es, L.L3, sd, s))
           return e;
-        GConvArgs g = L.fwd;
-        g.in = xs;
-        g.in_scale = g.in_shift = nullptr;
-        g.w = c.fptr(c.wimg(), L.wf_off);
-        g.bias = L.b_off >= 0 ? c.P + L.b_off : nullptr;
-        g.out = ys;
-        g.stats = nullptr;
-        g.partial = c.kpart();
-        if (int e = launch_conv_any(g, s)) return e;
+        if (int e = run_conv(L.fwd, xs, nullptr, nullptr, c.image(L.wf_off), c.param(L.b_off), ys, nullptr,
+                             c.kpart(), s))
+          return e;
         if (int e = launch_b2s(ys, y, p.B, L.out.X, L.out.Y, L.out.Z, L.out.Cs, es, L.L3, so, s)) return e;
       } else if (o.bn_relu) {
         if (int e = conv_forward(c, L, a.x, a.sc, a.sh, training)) return e;
       } else if (L.pw && !a.sc) {
         tag(L.name, "fwd");
-        PwArgs w{};
-        w.in = reinterpret_cast<const uint16_t *>(a.x);
-        w.w = c.P + L.w_off;
-        w.bias = L.b_off >= 0 ? c.P + L.b_off : nullptr;
-        w.out = reinterpret_cast<uint16_t *>(y);
-        w.nvox = L.out.vox();
-        w.ICs = L.in.Cs;
-        w.OCs = L.out.Cs;
-        w.Cin = L.Cin_g;
-        w.Cout = L.Cout;
-        w.part_c = L.part_c;
-        w.part_cs = L.part_cs;
-        if (int e = launch_pw(w, s)) return e;
+        if (int e = launch_pw(pw_args(L, false, a.x, c.P + L.w_off, c.param(L.b_off), y), s)) return e;
       } else {
         tag(L.name, "fwd");
-        GConvArgs g = L.fwd;
-        g.in = a.x;
-        g.in_scale = a.sc;
-        g.in_shift = a.sh;
-        g.w = c.fptr(c.wimg(), L.wf_off);
-        g.bias = L.b_off >= 0 ? c.P + L.b_off : nullptr;
-        g.out = y;
-        g.stats = nullptr;
-        g.partial = c.kpart();
-        if (int e = launch_conv_any(g, s)) return e;
+        if (int e = run_conv(L.fwd, a.x, a.sc, a.sh, c.image(L.wf_off), c.param(L.b_off), y, nullptr,
+                             c.kpart(), s))
+          return e;
       }
     } else if (o.kind == HCU_CHAIN_POOL) {
       const ConvLayer &P = p.chain[i - 1].conv;
@@ -2529,30 +2445,7 @@ int enqueue_chain_forward(const hcu_unet_plan &p, const hcu_unet_tensors *t, int
       tag(u.name, "fwd");
       const bool crop = o.crop[0] || o.crop[1] || o.crop[2];
       float *U = crop ? c.fptr(c.sc, p.ufull_off) : c.fptr(c.sv, u.u_off);
-      const float *bias = u.b_off >= 0 ? c.P + u.b_off : nullptr;
-      if (u.fused) {
-        GConvArgs g = u.fwdf;
-        g.in = a.x;
-        g.in_scale = a.sc;
-        g.in_shift = a.sh;
-        g.w = c.fptr(c.wimg(), u.wf_off);
-        g.bias = bias;
-        g.out = U;
-        g.stats = nullptr;
-        g.partial = c.kpart();
-        if (int e = launch_conv_any(g, s)) return e;
-      }
-      for (size_t ph = 0; !u.fused && ph < u.phases.size(); ++ph) {
-        GConvArgs g = u.phases[ph];
-        g.in = a.x;
-        g.in_scale = a.sc;
-        g.in_shift = a.sh;
-        g.w = c.fptr(c.wimg(), u.wph_off[ph]);
-        g.bias = bias;
-        g.out = U;
-        g.stats = nullptr;
-        if (int e = launch_gconv(g, s)) return e;
-      }
+      if (int e = convt_forward(c, u, a.x, a.sc, a.sh, U)) return e;
       if (crop) {
         const int sd[3] = {u.full.X, u.full.Y, u.full.Z}, dd[3] = {u.out.X, u.out.Y, u.out.Z};
         if (int e = launch_crop_cl(U, c.fptr(c.sv, u.u_off), p.B, sd, dd, o.crop, u.out.Cs, es, s)) return e;
@@ -2573,8 +2466,7 @@ int enqueue_chain_forward(const hcu_unet_plan &p, const hcu_unet_tensors *t, int
 int enqueue_chain_backward(const hcu_unet_plan &p, const hcu_unet_tensors *t, const float *dout, float *dx,
                            int training, int accumulate, hipStream_t s, void *images = nullptr,
                            int images_current = 0) {
-  Ctx c{p, *t, s, (char *)t->saved, (char *)t->scratch, t->params, t->grads};
-  if (images) c.wi = (char *)images - p.img_lo;
+  Ctx c(p, *t, s, false, images);
   const int es = p.es, bf = c.bf();
   const int n = (int)p.chain.size();
   const std::vector<ChainAct> in = chain_inputs(p, c.sv, t->x, nullptr);
@@ -2674,16 +2566,9 @@ int enqueue_chain_backward(const hcu_unet_plan &p, const hcu_unet_tensors *t, co
         if (int e = c.alloc(sd)) return e;
         dP = c.buf(sd);
       }
-      GConvArgs g = u.dgrad;
-      g.in = dU;
-      g.w = c.fptr(c.wimg(), u.wd_off);
-      g.out = dP;
-      g.partial = c.kpart();
       const ConvLayer *bnl = (pr && pr->kind == HCU_CHAIN_CONV && pr->bn_relu) ? &pr->conv : nullptr;
-      const bool fused = fuse_bnbwd(c, g, bnl);
-      if (int e = launch_conv_any(g, s)) return e;
-      if (fused)
-        if (int e = finish_bnbwd(c, g, *bnl, dP, training, accumulate)) return e;
+      bool fused = false;
+      if (int e = convt_dgrad(c, u, dU, dP, bnl, training, accumulate, fused)) return e;
       if (i == 0) {
         if (!p.in_cl)
           if (int e = launch_from_cl(dP, dx, p.B, p.xin.C, p.xin.Cs, p.xin.vox() / p.B, s, bf)) return e;
