@@ -59,6 +59,87 @@ class UnetTensors(ctypes.Structure):
     ]
 
 
+_X_DTYPES = {torch.float32: HCU_F32, torch.float16: HCU_F16, torch.bfloat16: HCU_BF16}
+
+
+def tensors(flat, bn, x, out, saved, scratch, grads=None):
+    """hcu_unet_tensors of one executor call: `flat` the parameter buffer, `bn`
+    the BNArrays of the plan's BatchNorm layers."""
+    rm, rv, nb = bn.get()
+    t = UnetTensors()
+    t.x = x.data_ptr()
+    t.out = out.data_ptr() if out is not None else None
+    t.params = flat.data_ptr()
+    t.grads = grads.data_ptr() if grads is not None else None
+    t.bn_running_mean = ctypes.cast(rm, ctypes.POINTER(ctypes.c_void_p))
+    t.bn_running_var = ctypes.cast(rv, ctypes.POINTER(ctypes.c_void_p))
+    t.bn_num_batches_tracked = ctypes.cast(nb, ctypes.POINTER(ctypes.c_void_p))
+    t.saved = saved.data_ptr()
+    t.scratch = scratch.data_ptr()
+    t.x_dtype = _X_DTYPES[x.dtype]
+    return t
+
+
+class BNArrays:
+    """The three pointer arrays (running mean, running var, batch count) of a
+    list of BatchNorm modules, rebuilt when a running-mean buffer moved."""
+
+    def __init__(self, bns):
+        self.bns = bns
+        self._ptrs = None
+        self._arrays = None
+
+    def get(self):
+        bns = self.bns
+        ptrs = [bn.running_mean.data_ptr() for bn in bns]
+        if ptrs != self._ptrs:
+            for bn in bns:
+                if bn.running_mean.dtype != torch.float32 or not bn.running_mean.is_contiguous():
+                    raise RuntimeError('hcunet_amd: BatchNorm running stats must be contiguous fp32')
+            n = max(1, len(bns))
+            self._arrays = ((ctypes.c_void_p * n)(*ptrs),
+                            (ctypes.c_void_p * n)(*[bn.running_var.data_ptr() for bn in bns]),
+                            (ctypes.c_void_p * n)(*[bn.num_batches_tracked.data_ptr() for bn in bns]))
+            self._ptrs = ptrs
+        return self._arrays
+
+
+class Plan:
+    """Owner of one native plan handle and the sizes every plan reports.
+    create(byref(handle)) and query(handle, out_shape, n_bn, saved, scratch)
+    are the U-Net's or the chains' calls; both kinds are destroyed by
+    hcu_unet_plan_destroy."""
+
+    def __init__(self, create, query, what):
+        handle = ctypes.c_void_p()
+        check(create(ctypes.byref(handle)), what)
+        self.handle = handle
+        out_shape = (ctypes.c_int64 * 5)()
+        n_bn = ctypes.c_int()
+        saved, scratch = ctypes.c_size_t(), ctypes.c_size_t()
+        check(query(handle, out_shape, ctypes.byref(n_bn), ctypes.byref(saved), ctypes.byref(scratch)))
+        self.out_shape = tuple(int(v) for v in out_shape)
+        self.n_bn = int(n_bn.value)
+        self.saved_bytes = int(saved.value)
+        self.scratch_bytes = int(scratch.value)
+
+    def __del__(self):
+        try:
+            if self.handle:
+                lib().hcu_unet_plan_destroy(self.handle)
+        except Exception:
+            pass
+
+
+def t3(v):
+    if isinstance(v, int):
+        return (v, v, v)
+    v = tuple(v)
+    if len(v) != 3:
+        raise ValueError('expected an int or a 3-tuple, got %r' % (v,))
+    return v
+
+
 class ConvDesc(ctypes.Structure):
     _fields_ = [
         ("B", ctypes.c_int), ("Cin", ctypes.c_int), ("Cout", ctypes.c_int),

@@ -9,11 +9,10 @@ backward in the consumer dgrad's epilogue).  It is what calling a single
 Down / Up block runs (hcat/unet.py:263-266, 309-315) and what the
 r_unet.py models are built from (hcat/r_unet.py:207-378).
 
-Parameters of the modules a chain reads are views of one flat fp32 buffer
-(FlatParams), gradients are accumulated into a second one whose views are
-attached as .grad (torch's accumulation semantics), so a model that calls
-many chains per step (the 10-step recurrences of r_unet.py) gathers every
-gradient in place.
+Parameters and gradients live in the flat store of hcunet_amd.flat
+(FlatParams, the accumulate rule of grad_target), so a model that calls many
+chains per step (the 10-step recurrences of r_unet.py) gathers every gradient
+in place.
 """
 import ctypes
 
@@ -21,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .flat import FlatParams
 
 CONV, POOL, CONVT = 0, 1, 2
 MAX_OPS = 16
@@ -49,106 +49,6 @@ class ChainSpec(ctypes.Structure):
     ]
 
 
-def _t3(v):
-    if isinstance(v, int):
-        return (v, v, v)
-    v = tuple(v)
-    if len(v) != 3:
-        raise ValueError('expected an int or a 3-tuple, got %r' % (v,))
-    return v
-
-
-# ---------------------------------------------------------------------------
-class FlatParams:
-    """The parameters of `root` as views of one flat fp32 device buffer, and a
-    flat gradient buffer of the same layout (hcunet_amd.unet._Engine does the
-    same for Unet_Constructor).  Parameters that are already views of one
-    contiguous fp32 storage (a Unet_Constructor whose engine flattened them)
-    are used in place."""
-
-    def __init__(self, root):
-        self.root = root
-        self.flat = None
-        self.grad = None
-        self.params = None
-        self.offsets = {}
-
-    def ready(self):
-        params = [p for p in self.root.parameters()]
-        if self.flat is not None and len(params) == len(self.params) and all(
-                p is q and p.data_ptr() == self.flat.data_ptr() + 4 * self.offsets[id(p)]
-                for p, q in zip(params, self.params)):
-            return self
-        dev = params[0].device
-        _lib.require_device(params[0], 'module parameters')
-        for p in params:
-            if p.dtype != torch.float32 or p.device != dev:
-                raise RuntimeError('hcunet_amd: parameters must be float32 on one device')
-        st = {p.untyped_storage().data_ptr() for p in params}
-        if len(st) == 1 and all(p.is_contiguous() for p in params):
-            # views of one buffer (e.g. the flat parameters of a Unet_Constructor)
-            store = params[0].untyped_storage()
-            base = torch.empty(0, dtype=torch.float32, device=dev).set_(
-                store, 0, (store.nbytes() // 4,), (1,))
-            self.flat = base
-            self.offsets = {id(p): p.storage_offset() for p in params}
-        else:
-            n = sum(p.numel() for p in params)
-            flat = torch.empty(n, dtype=torch.float32, device=dev)
-            off = 0
-            self.offsets = {}
-            with torch.no_grad():
-                for p in params:
-                    k = p.numel()
-                    flat[off:off + k].copy_(p.data.reshape(-1))
-                    p.data = flat[off:off + k].view_as(p)
-                    self.offsets[id(p)] = off
-                    off += k
-            self.flat = flat
-        self.params = params
-        self.grad = None
-        return self
-
-    def offset(self, p):
-        return self.offsets[id(p)] if p is not None else -1
-
-    def grad_target(self):
-        """(buffer, finish): gradients accumulate into `buffer`; finish()
-        attaches / adds them with torch's .grad semantics."""
-        params = self.params
-        n = self.flat.numel()
-        if self.grad is None or self.grad.numel() != n or self.grad.device != self.flat.device:
-            self.grad = torch.zeros(n, dtype=torch.float32, device=self.flat.device)
-        G = self.grad
-        base = G.data_ptr()
-
-        def view(p):
-            o = self.offsets[id(p)]
-            return G[o:o + p.numel()].view_as(p)
-        trainable = [p for p in params if p.requires_grad]
-        if all(p.grad is None for p in trainable):
-            G.zero_()
-
-            def finish():
-                for p in trainable:
-                    p.grad = view(p)
-            return G, finish
-        if all(p.grad is not None and p.grad.data_ptr() == base + 4 * self.offsets[id(p)]
-               for p in trainable):
-            return G, (lambda: None)
-        tmp = torch.zeros_like(self.flat)
-
-        def finish_mixed():
-            for p in trainable:
-                o = self.offsets[id(p)]
-                g = tmp[o:o + p.numel()].view_as(p)
-                if p.grad is None:
-                    p.grad = g.clone()
-                else:
-                    p.grad.add_(g)
-        return tmp, finish_mixed
-
-
 # ---------------------------------------------------------------------------
 class Chain:
     """One op sequence over modules of `flat.root`.  ops: list of tuples
@@ -169,8 +69,8 @@ class Chain:
         self.in_channels = in_channels
         self.ops = ops
         self.bns = [op[2] for op in ops if op[0] == 'conv' and op[2] is not None]
+        self.bn = _lib.BNArrays(self.bns)
         self.plans = {}
-        self._bn_arrays = None
 
     def spec(self, bf16):
         s = ChainSpec()
@@ -208,7 +108,7 @@ class Chain:
                     eps, mom = bn.eps, bn.momentum
             elif op[0] == 'pool':
                 o.kind = POOL
-                o.k = _lib.c_int3(*_t3(op[1]))
+                o.k = _lib.c_int3(*_lib.t3(op[1]))
             elif op[0] == 'convt':
                 ct = op[1]
                 if any(v != 0 for v in ct.output_padding) or ct.groups != 1 or tuple(ct.dilation) != (1, 1, 1):
@@ -259,16 +159,6 @@ class Chain:
             self.plans[key] = p
         return p
 
-    def bn_arrays(self):
-        ptrs = [bn.running_mean.data_ptr() for bn in self.bns]
-        if self._bn_arrays is None or self._bn_arrays[3] != ptrs:
-            n = max(1, len(self.bns))
-            rm = (ctypes.c_void_p * n)(*[bn.running_mean.data_ptr() for bn in self.bns])
-            rv = (ctypes.c_void_p * n)(*[bn.running_var.data_ptr() for bn in self.bns])
-            nb = (ctypes.c_void_p * n)(*[bn.num_batches_tracked.data_ptr() for bn in self.bns])
-            self._bn_arrays = (rm, rv, nb, ptrs)
-        return self._bn_arrays
-
     def __call__(self, x, training, bf16=False):
         self.flat.ready()
         params = self.flat.params
@@ -304,23 +194,14 @@ def _weight_key(chain):
     return (chain.flat.flat.data_ptr(), _WEIGHT_EPOCH[0]) + tuple(p._version for p in chain.flat.params)
 
 
-class _ChainPlan:
+class _ChainPlan(_lib.Plan):
     def __init__(self, spec, B, X, Y, Z):
         L = _lib.lib()
-        h = ctypes.c_void_p()
-        _lib.check(L.hcu_chain_plan_create(ctypes.addressof(spec), B, X, Y, Z, ctypes.byref(h)), 'chain')
-        self.handle = h
-        out = (ctypes.c_int64 * 5)()
-        nbn = ctypes.c_int()
-        sv, sc = ctypes.c_size_t(), ctypes.c_size_t()
-        _lib.check(L.hcu_chain_plan_query(h, out, ctypes.byref(nbn), ctypes.byref(sv), ctypes.byref(sc)))
-        self.out_shape = tuple(int(v) for v in out)
-        self.n_bn = int(nbn.value)
-        self.saved_bytes = int(sv.value)
-        self.scratch_bytes = int(sc.value)
+        super().__init__(lambda h: L.hcu_chain_plan_create(ctypes.addressof(spec), B, X, Y, Z, h),
+                         L.hcu_chain_plan_query, 'chain')
         # packed weight images kept across calls (the last image_bytes of
         # `saved` otherwise): re-laid only when the parameters changed
-        self.image_bytes = int(L.hcu_chain_weight_image_bytes(h))
+        self.image_bytes = int(L.hcu_chain_weight_image_bytes(self.handle))
         self.images = None
         self.image_key = None
         self.image_level = 0   # 1: forward images of image_key, 2: also the input-gradient ones
@@ -333,32 +214,6 @@ class _ChainPlan:
         if key != self.image_key:
             self.image_key, self.image_level = key, 0
         return self.images, self.image_level
-
-    def __del__(self):
-        try:
-            if self.handle:
-                _lib.lib().hcu_unet_plan_destroy(self.handle)
-        except Exception:
-            pass
-
-
-_X_DTYPES = {torch.float32: _lib.HCU_F32, torch.float16: _lib.HCU_F16, torch.bfloat16: _lib.HCU_BF16}
-
-
-def _tensors(chain, x, out, saved, scratch, grads=None):
-    rm, rv, nb, _ = chain.bn_arrays()
-    t = _lib.UnetTensors()
-    t.x = x.data_ptr()
-    t.out = out.data_ptr() if out is not None else None
-    t.params = chain.flat.flat.data_ptr()
-    t.grads = grads.data_ptr() if grads is not None else None
-    t.bn_running_mean = ctypes.cast(rm, ctypes.POINTER(ctypes.c_void_p))
-    t.bn_running_var = ctypes.cast(rv, ctypes.POINTER(ctypes.c_void_p))
-    t.bn_num_batches_tracked = ctypes.cast(nb, ctypes.POINTER(ctypes.c_void_p))
-    t.saved = saved.data_ptr()
-    t.scratch = scratch.data_ptr()
-    t.x_dtype = _X_DTYPES[x.dtype]
-    return t
 
 
 class _ChainFunction(torch.autograd.Function):
@@ -377,7 +232,7 @@ class _ChainFunction(torch.autograd.Function):
         # `saved` is not needed)
         saved = torch.empty(max(plan.saved_bytes - plan.image_bytes, 1), dtype=torch.uint8, device=dev)
         scratch = torch.empty(max(plan.scratch_bytes, 1), dtype=torch.uint8, device=dev)
-        t = _tensors(chain, x, out, saved, scratch)
+        t = _lib.tensors(chain.flat.flat, chain.bn, x, out, saved, scratch)
         L = _lib.lib()
         if TAG_CHAINS:
             L.hcu_timing_prefix(chain.name.encode())
@@ -417,15 +272,15 @@ class _ChainFunction(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(x.shape, dtype=x.dtype if chain.in_cl else torch.float32, device=dev)
-        G, finish = chain.flat.grad_target()
-        t = _tensors(chain, x, None, saved, scratch, grads=G)
+        G, accumulate, finish = chain.flat.grad_target(overwrite=False)
+        t = _lib.tensors(chain.flat.flat, chain.bn, x, None, saved, scratch, grads=G)
         L = _lib.lib()
         if TAG_CHAINS:
             L.hcu_timing_prefix(chain.name.encode())
         with torch.cuda.device(dev):
             _lib.check(L.hcu_chain_backward_images(plan.handle, ctypes.byref(t),
                                                    ctypes.c_void_p(dout.data_ptr()), _lib.ptr(dx),
-                                                   1 if ctx.training else 0, 1, _lib.stream_handle(dev),
+                                                   1 if ctx.training else 0, accumulate, _lib.stream_handle(dev),
                                                    ctypes.c_void_p(plan.images.data_ptr()), plan.image_level),
                        'chain backward')
         plan.image_level = 2
@@ -445,8 +300,8 @@ def cl_channels(c, bf16):
 
 
 def flat_of(module, root=None):
-    """The FlatParams of `root` (default: module), created on first use and
-    kept on the root module."""
+    """The FlatParams (hcunet_amd.flat) of `root` (default: module), created on
+    first use and kept on the root module."""
     root = root if root is not None else module
     f = root.__dict__.get('_hcu_flat')
     if f is None:

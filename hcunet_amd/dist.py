@@ -16,6 +16,8 @@ import weakref
 import torch
 import torch.distributed as dist
 
+from .flat import flat_run
+
 
 def _avg_supported(group=None):
     return dist.get_backend(group) == 'nccl'
@@ -142,16 +144,11 @@ def allreduce_gradients(module, group=None, bn_stats=True):
     G = getattr(eng, 'grad_flat', None) if eng is not None else None
     C = getattr(eng, 'comm_flat', None) if eng is not None else None
     nstat = sum(t.numel() for t in stats)
-    flat_ok = False
-    if G is not None and C is not None and params and len(params) == len(list(module.parameters())):
-        base, off, flat_ok = G.data_ptr(), 0, True
-        for p in params:
-            if p.grad.data_ptr() != base + 4 * off:
-                flat_ok = False
-                break
-            off += p.numel()
-        flat_ok = flat_ok and off == G.numel() and C.data_ptr() == base \
-            and C.numel() >= G.numel() + nstat
+    F = _flat_grads(params)
+    flat_ok = F is not None and G is not None and C is not None \
+        and len(params) == len(list(module.parameters())) \
+        and F.data_ptr() == G.data_ptr() and F.numel() == G.numel() \
+        and C.data_ptr() == G.data_ptr() and C.numel() >= G.numel() + nstat
     native = flat_ok and C.is_cuda and 0 < len(stats) <= 128 and all(t.is_contiguous() for t in stats)
     ev = getattr(eng, 'grad_events', None) if eng is not None else None
     # the overlapped ranges wait only for the backward's own events: any
@@ -172,10 +169,9 @@ def allreduce_gradients(module, group=None, bn_stats=True):
         elif stats:
             torch.cat([t.reshape(-1) for t in stats], out=tail)
     else:
-        F = _flat_grads(params)
         if F is not None and not stats:
             # the layer chains' models (RDCNet, RecursiveUnet without running
-            # statistics, hcunet_amd.chain.FlatParams): every .grad is a view
+            # statistics, hcunet_amd.flat.FlatParams): every .grad is a view
             # of one flat buffer in parameter order -- reduced in place
             _reduce(F, group, world)
             return
@@ -206,19 +202,9 @@ def allreduce_gradients(module, group=None, bn_stats=True):
 def _flat_grads(params):
     """The gradients as ONE flat tensor when every .grad is a contiguous
     view of one storage, in parameter order without gaps (what
-    hcunet_amd.chain.FlatParams attaches), else None."""
-    g0 = params[0].grad
-    if g0.dtype != torch.float32:
-        return None
-    st, base, off = g0.untyped_storage().data_ptr(), g0.data_ptr(), 0
-    for p in params:
-        g = p.grad
-        if g.dtype != torch.float32 or not g.is_contiguous() or g.untyped_storage().data_ptr() != st \
-                or g.data_ptr() != base + 4 * off:
-            return None
-        off += g.numel()
-    return torch.empty(0, dtype=torch.float32, device=g0.device).set_(
-        g0.untyped_storage(), g0.storage_offset(), (off,), (1,))
+    hcunet_amd.flat.FlatParams attaches), else None."""
+    run = flat_run([p.grad for p in params])
+    return run[0] if run is not None else None
 
 
 def _allreduce_overlapped(eng, buf, n_grads, stats, ranges, ev, group, world):

@@ -15,21 +15,7 @@ import torch
 from torch.optim import optimizer as _topt
 
 from . import _lib
-
-
-def _flat_run(tensors):
-    """(base tensor of the run, total numel) if `tensors` are consecutive fp32
-    views of one storage, else None."""
-    if not tensors:
-        return None
-    t0 = tensors[0]
-    base = t0.data_ptr()
-    off = 0
-    for t in tensors:
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() != base + 4 * off:
-            return None
-        off += t.numel()
-    return t0, off
+from .flat import flat_run as _flat_run
 
 
 class Adam(torch.optim.Optimizer):

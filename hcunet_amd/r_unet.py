@@ -32,6 +32,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import chain as _chain_mod
+from ._lib import t3 as _t3
 from .chain import Chain, bf16_active, cl_channels, flat_of, upsample_cat_check
 
 
@@ -56,10 +57,6 @@ def _chain(owner, root, name, in_channels, ops, **cl):
         ch = Chain(flat_of(root), in_channels, ops, '%s.%s' % (type(owner).__name__, name), **cl)
         cache[key] = ch
     return ch
-
-
-def _t3(v):
-    return (v, v, v) if isinstance(v, int) else tuple(v)
 
 
 def _pool_k(mp):
@@ -236,7 +233,7 @@ class _PwConv(torch.autograd.Function):
         L = _lib.lib()
         need = any(ctx.needs_input_grad[4:])
         dparts = [torch.empty_like(p) for p in parts] if need else None
-        G, finish = flat.grad_target()
+        G, _, finish = flat.grad_target(overwrite=False)
         base = G.data_ptr()
         dw = ctypes.c_void_p(base + 4 * flat.offset(conv.weight))
         db = ctypes.c_void_p(base + 4 * flat.offset(conv.bias)) if conv.bias is not None else ctypes.c_void_p()

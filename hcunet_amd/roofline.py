@@ -16,13 +16,11 @@ the sum over layers.  Rules:
 Shapes follow hcat/unet.py:125-143 (valid convolutions, floor pooling,
 ConvTranspose3d out = (in - 1) * s + k).
 """
+from ._lib import t3 as _t3
+
 PEAK_HBM = 8.0e12          # B/s, MI355X HBM3E (MI355X_MICROARCH.md)
 PEAK_FP32 = 157.3e12       # FLOP/s dense fp32 MFMA
 PEAK_BF16 = 2.5e15         # FLOP/s dense bf16 MFMA
-
-
-def _t3(v):
-    return (v, v, v) if isinstance(v, int) else tuple(v)
 
 
 def layers(kw, B, shape, bf16=False):

@@ -20,10 +20,9 @@ arithmetic.  Under torch.autocast('cuda', dtype=torch.bfloat16) (or with
 config 3: bf16 activations, gradients and MFMA operands, fp32 accumulation,
 BatchNorm statistics, parameters and optimizer state; the input may then be a
 fp32, fp16 or bf16 volume (16-bit volumes are read directly by the first
-kernel), and the logits are returned in fp32.  Parameters live in one flat fp32 buffer (each nn.Parameter is
-a view of it) and gradients are written into one flat buffer whose views are
-attached as .grad, so the optimizer step and the data-parallel all-reduce are
-single launches over contiguous memory.
+kernel), and the logits are returned in fp32.  Parameters and gradients live
+in the flat store of hcunet_amd.flat (FlatParams, the overwrite rule of
+grad_target).
 """
 import ctypes
 import glob
@@ -33,6 +32,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .chain import Chain, bf16_active, flat_of, upsample_cat_check
+from .flat import FlatParams
 
 
 # ---------------------------------------------------------------------------
@@ -122,13 +123,9 @@ class Unet_Constructor(nn.Module):
         return self._engine
 
     def _bf16(self):
-        cd = getattr(self, 'compute_dtype', None)
-        if cd is not None:
-            if cd not in (torch.float32, torch.bfloat16):
-                raise ValueError('compute_dtype must be torch.float32 or torch.bfloat16')
-            return cd == torch.bfloat16
-        return bool(torch.is_autocast_enabled('cuda')
-                    and torch.get_autocast_dtype('cuda') == torch.bfloat16)
+        if getattr(self, 'compute_dtype', None) not in (None, torch.float32, torch.bfloat16):
+            raise ValueError('compute_dtype must be torch.float32 or torch.bfloat16')
+        return bf16_active(self)
 
     def forward(self, x):
         if not isinstance(x, torch.Tensor):
@@ -222,7 +219,6 @@ class Down(nn.Module):
         """hcat/unet.py:263-266 as one layer chain (hcunet_amd.chain):
         conv1 -> BN -> ReLU -> conv2 -> BN -> ReLU."""
         _lib.require_device(x, 'Down input')
-        from .chain import Chain, bf16_active, flat_of
         ch = self.__dict__.get('_hcu_chain')
         if ch is None:
             ch = Chain(flat_of(self), self.conv1.in_channels,
@@ -263,9 +259,8 @@ class Up(nn.Module):
         up_conv -> cat(U, crop(U, y)) = cat(U, U) -> conv1 -> BN -> ReLU ->
         conv2 -> BN -> ReLU."""
         _lib.require_device(x, 'Up input')
-        from .chain import Chain, bf16_active, flat_of, upsample_cat_check
-        k, st, pd = (_triple(self.up_conv.kernel_size), _triple(self.up_conv.stride),
-                     _triple(self.up_conv.padding))
+        k, st, pd = (_lib.t3(self.up_conv.kernel_size), _lib.t3(self.up_conv.stride),
+                     _lib.t3(self.up_conv.padding))
         u = [x.shape[0], self.up_conv.out_channels] + [(x.shape[2 + d] - 1) * st[d] - 2 * pd[d] + k[d]
                                                        for d in range(3)]
         upsample_cat_check(u, y)
@@ -290,15 +285,6 @@ def crop(x, y):
 
 
 # ---------------------------------------------------------------------------
-def _triple(v):
-    if isinstance(v, int):
-        return (v, v, v)
-    v = tuple(v)
-    if len(v) != 3:
-        raise ValueError('expected an int or a 3-tuple, got %r' % (v,))
-    return v
-
-
 def spec_struct(module):
     """hcu_unet_spec for a 3D Unet_Constructor (parameters read from its modules)."""
     s = module.model_specification
@@ -326,10 +312,10 @@ def spec_struct(module):
                            % (u0.up_conv.kernel_size,))
     spec.up_k = _lib.c_int3(*u0.up_conv.kernel_size)
     spec.up_s = _lib.c_int3(*u0.up_conv.stride)
-    spec.pool_k = _lib.c_int3(*_triple(module.max_pool.kernel_size))
+    spec.pool_k = _lib.c_int3(*_lib.t3(module.max_pool.kernel_size))
     mp = module.max_pool
-    if _triple(mp.stride) != _triple(mp.kernel_size) or _triple(mp.padding) != (0, 0, 0) \
-            or _triple(mp.dilation) != (1, 1, 1) or mp.ceil_mode:
+    if _lib.t3(mp.stride) != _lib.t3(mp.kernel_size) or _lib.t3(mp.padding) != (0, 0, 0) \
+            or _lib.t3(mp.dilation) != (1, 1, 1) or mp.ceil_mode:
         raise NotImplementedError('max_pool must be kernel == stride, no padding, floor mode')
     bns = bn_modules(module)
     eps, mom = bns[0].eps, bns[0].momentum
@@ -359,64 +345,49 @@ def bn_modules(module):
     return out
 
 
-class _Plan:
+class _Plan(_lib.Plan):
     def __init__(self, spec, B, X, Y, Z, flags=0):
         L = _lib.lib()
-        handle = ctypes.c_void_p()
-        _lib.check(L.hcu_unet_plan_create_ex(ctypes.byref(spec), B, X, Y, Z, flags,
-                                             ctypes.byref(handle)),
-                   'Unet_Constructor')
-        self.handle = handle
-        out_shape = (ctypes.c_int64 * 5)()
         n_params = ctypes.c_int64()
-        n_bn = ctypes.c_int()
-        saved = ctypes.c_size_t()
-        scratch = ctypes.c_size_t()
-        _lib.check(L.hcu_unet_plan_query(handle, out_shape, ctypes.byref(n_params),
-                                         ctypes.byref(n_bn), ctypes.byref(saved),
-                                         ctypes.byref(scratch)))
-        self.out_shape = tuple(int(v) for v in out_shape)
+        super().__init__(
+            lambda h: L.hcu_unet_plan_create_ex(ctypes.byref(spec), B, X, Y, Z, flags, h),
+            lambda h, out_shape, *sizes: L.hcu_unet_plan_query(h, out_shape, ctypes.byref(n_params), *sizes),
+            'Unet_Constructor')
         self.n_params = int(n_params.value)
-        self.n_bn = int(n_bn.value)
-        self.saved_bytes = int(saved.value)
-        self.scratch_bytes = int(scratch.value)
-
-    def __del__(self):
-        try:
-            if self.handle:
-                _lib.lib().hcu_unet_plan_destroy(self.handle)
-        except Exception:
-            pass
 
 
 class _Engine:
-    """Per-module native state: plans per input shape, flat params/grads."""
+    """Per-module native state: plans per input shape, the flat store."""
 
     def __init__(self, module):
         self.module_ref = module
         self.spec = spec_struct(module)
         self.plans = {}
-        self.flat = None
-        self.grad_flat = None
-        # grad_flat is the head of comm_flat; the tail is room for the BatchNorm
-        # running statistics, so a data-parallel step reduces both in ONE
-        # collective (hcunet_amd.dist.allreduce_gradients).
-        self.comm_flat = None
-        self.params = None
-        self._slots = None   # (module, name) of each parameter, in self.params order
-        self._bns = None
-        self._bn_arrays = None
+        # packed: the executor derives every offset from the spec.  The tail
+        # behind the gradients is room for the BatchNorm running statistics
+        # (hcunet_amd.dist.allreduce_gradients reduces both in ONE collective).
+        self.store = FlatParams(module, 'Unet_Constructor parameters', packed=True)
+        bns = bn_modules(module)
+        self.store.stats_tail = 2 * sum(bn.num_features for bn in bns)
+        self.bn = _lib.BNArrays(bns)
         # data-parallel overlap (hcunet_amd.dist.prepare_overlap): native events
         # the backward records when gradient groups are final, and whether the
         # last backward recorded them into grad_flat
         self.grad_events = None      # (ev_decoder, ev_deep, deep_level) or None
         self.events_recorded = False
         self.grad_version = None     # grad_flat._version right after the last backward
-        # per-parameter views of grad_flat, made once per grad_flat (attaching
-        # a cached view costs the host ~0.4 us, slicing a new one ~5 us: 82
-        # parameters per step)
-        self._grad_views = None
         self._token = None           # the autograd input that stands for the parameters
+
+    flat = property(lambda self: self.store.flat)
+    params = property(lambda self: self.store.params)
+    grad_flat = property(lambda self: self.store.grad)
+    comm_flat = property(lambda self: self.store.comm)
+
+    def params_ready(self, require_gpu=True):
+        return self.store.ready(require_gpu).params
+
+    def grad_target(self):
+        return self.store.grad_target(overwrite=True)
 
     def token(self, dev):
         t = self._token
@@ -450,162 +421,8 @@ class _Engine:
             self.plans[key] = p
         return p
 
-    def params_ready(self, require_gpu=True):
-        """Ensure every parameter is a view of one flat fp32 buffer (a device
-        buffer for the native path; require_gpu=False lays out host tensors the
-        same way, for the CPU tests of the data-parallel host logic).  The
-        per-step check follows the (module, name) slots recorded at layout
-        time: a replaced Parameter or moved storage is detected; a whole
-        submodule swapped into the network after the first forward is not
-        (rebuild the model, as the reference's own load() does)."""
-        m = self.module_ref
-        flat = self.flat
-        ok = flat is not None and self.params is not None and self._slots is not None
-        if ok:
-            # fast path: the (module, name) slots recorded at layout time still
-            # hold the same Parameter objects, each still a view of the flat
-            # buffer (no recursive module walk per step: host time)
-            base = flat.data_ptr()
-            off = 0
-            for (mod, name), q in zip(self._slots, self.params):
-                if mod._parameters.get(name) is not q or q.data_ptr() != base + 4 * off:
-                    ok = False
-                    break
-                off += q.numel()
-        if ok:
-            return self.params
-        params = list(m.parameters())
-        ok = flat is not None and self.params is not None and len(params) == len(self.params)
-        if ok:
-            base = flat.data_ptr()
-            off = 0
-            for p, q in zip(params, self.params):
-                if p is not q or p.data_ptr() != base + 4 * off:
-                    ok = False
-                    break
-                off += p.numel()
-        if ok:
-            self._slots = [(mod, name) for _, mod in m.named_modules()
-                           for name, prm in mod._parameters.items() if prm is not None]
-            if len(self._slots) != len(params) or any(mod._parameters[n] is not q
-                                                      for (mod, n), q in zip(self._slots, params)):
-                self._slots = None
-        if not ok:
-            dev = params[0].device
-            for p in params:
-                if p.dtype != torch.float32:
-                    raise RuntimeError('hcunet_amd: parameters must be float32')
-                if p.device != dev:
-                    raise RuntimeError('hcunet_amd: parameters on several devices')
-            if require_gpu:
-                _lib.require_device(params[0], 'Unet_Constructor parameters')
-            n = sum(p.numel() for p in params)
-            flat = torch.empty(n, dtype=torch.float32, device=dev)
-            off = 0
-            with torch.no_grad():
-                for p in params:
-                    k = p.numel()
-                    flat[off:off + k].copy_(p.data.reshape(-1))
-                    p.data = flat[off:off + k].view_as(p)
-                    off += k
-            self.flat = flat
-            self.params = params
-            self.grad_flat = None
-            self.comm_flat = None
-            self._bn_arrays = None
-            self._slots = [(mod, name) for _, mod in m.named_modules()
-                           for name, prm in mod._parameters.items() if prm is not None]
-            if len(self._slots) != len(params) or any(mod._parameters[n] is not q
-                                                      for (mod, n), q in zip(self._slots, params)):
-                self._slots = None   # unusual registration order: keep the full check
-        return self.params
-
-    def bn_arrays(self):
-        if self._bn_arrays is None:
-            bns = bn_modules(self.module_ref)
-            self._bns = bns
-            for bn in bns:
-                if bn.running_mean.dtype != torch.float32 or not bn.running_mean.is_contiguous():
-                    raise RuntimeError('hcunet_amd: BatchNorm running stats must be contiguous fp32')
-            n = len(bns)
-            rm = (ctypes.c_void_p * n)(*[bn.running_mean.data_ptr() for bn in bns])
-            rv = (ctypes.c_void_p * n)(*[bn.running_var.data_ptr() for bn in bns])
-            nb = (ctypes.c_void_p * n)(*[bn.num_batches_tracked.data_ptr() for bn in bns])
-            self._bn_arrays = (rm, rv, nb, [bn.running_mean.data_ptr() for bn in bns])
-        else:
-            bns = self._bns
-            if [bn.running_mean.data_ptr() for bn in bns] != self._bn_arrays[3]:
-                self._bn_arrays = None
-                return self.bn_arrays()
-        return self._bn_arrays
-
-    def tensors(self, x, out, saved, scratch, grads=None):
-        rm, rv, nb, _ = self.bn_arrays()
-        t = _lib.UnetTensors()
-        t.x = x.data_ptr()
-        t.out = out.data_ptr() if out is not None else None
-        t.params = self.flat.data_ptr()
-        t.grads = grads.data_ptr() if grads is not None else None
-        t.bn_running_mean = ctypes.cast(rm, ctypes.POINTER(ctypes.c_void_p))
-        t.bn_running_var = ctypes.cast(rv, ctypes.POINTER(ctypes.c_void_p))
-        t.bn_num_batches_tracked = ctypes.cast(nb, ctypes.POINTER(ctypes.c_void_p))
-        t.saved = saved.data_ptr()
-        t.scratch = scratch.data_ptr()
-        t.x_dtype = _X_DTYPES[x.dtype]
-        return t
-
-    def grad_target(self):
-        """Decide where backward writes parameter gradients.
-
-        Returns (buffer, accumulate, finish) where finish() attaches/adds the
-        gradients with torch's .grad accumulation semantics."""
-        params = self.params
-        if self.grad_flat is None or self.grad_flat.numel() != self.flat.numel() \
-                or self.grad_flat.device != self.flat.device:
-            n_stats = 2 * sum(bn.num_features for bn in bn_modules(self.module_ref))
-            self.comm_flat = torch.zeros(self.flat.numel() + n_stats, dtype=torch.float32,
-                                         device=self.flat.device)
-            self.grad_flat = self.comm_flat[:self.flat.numel()]
-        G = self.grad_flat
-        views = self._grad_views
-        if views is None or views[0] is not G or len(views[1]) != len(params):
-            offs, vs, off = [], [], 0
-            for p in params:
-                offs.append(off)
-                vs.append(G[off:off + p.numel()].view_as(p))
-                off += p.numel()
-            views = self._grad_views = (G, vs, offs)
-        _, vs, offs = views
-        grads = [p.grad for p in params]
-        if all(g is None for g in grads):
-            def finish():
-                for p, v in zip(params, vs):
-                    if p.requires_grad:
-                        p.grad = v
-            return G, 0, finish
-        if all(g is v for g, v in zip(grads, vs)):
-            return G, 1, (lambda: None)
-        base = G.data_ptr()
-        if all(g is not None and g.data_ptr() == base + 4 * o and g.shape == p.shape
-               for p, g, o in zip(params, grads, offs)):
-            return G, 1, (lambda: None)
-        tmp = torch.empty_like(self.flat)
-
-        def finish_mixed():
-            for p, o in zip(params, offs):
-                if not p.requires_grad:
-                    continue
-                g = tmp[o:o + p.numel()].view_as(p)
-                if p.grad is None:
-                    p.grad = g.clone()
-                else:
-                    p.grad.add_(g)
-        return tmp, 0, finish_mixed
-
 
 _POISON = os.environ.get('HCU_POISON') == '1'
-_X_DTYPES = {torch.float32: _lib.HCU_F32, torch.float16: _lib.HCU_F16,
-             torch.bfloat16: _lib.HCU_BF16}
 
 
 class _NoCtx:
@@ -638,7 +455,7 @@ class _UnetFunction(torch.autograd.Function):
             saved.fill_(255)
             scratch.fill_(255)
         training = 1 if eng.module_ref.training else 0
-        t = eng.tensors(x, out, saved, scratch)
+        t = _lib.tensors(eng.flat, eng.bn, x, out, saved, scratch)
         # The executor's graph-capture and side streams are created on the
         # current device: make it the tensors' device.
         with _on_device(dev):
@@ -666,7 +483,7 @@ class _UnetFunction(torch.autograd.Function):
             scratch.fill_(255)
         dx = torch.empty(x.shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         G, accumulate, finish = eng.grad_target()
-        t = eng.tensors(x, None, saved, scratch, grads=G)
+        t = _lib.tensors(eng.flat, eng.bn, x, None, saved, scratch, grads=G)
         ev = eng.grad_events if G is eng.grad_flat else None
         L = _lib.lib()
         if ev is not None and not L.hcu_unet_grad_events_live(plan.handle):

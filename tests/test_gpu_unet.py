@@ -292,3 +292,82 @@ def test_grad_accumulation_and_input_grad():
     xr = torch.from_numpy(x).double().requires_grad_(True)
     net.forward(xr).sum().backward()
     assert (dx - xr.grad).abs().max().item() <= 1e-5 * xr.grad.abs().max().item() + 1e-7
+
+
+def _weighted_backward(out, seed):
+    w = torch.randn(out.shape, generator=torch.Generator().manual_seed(seed)).to(out.device)
+    (out * w).sum().backward()
+
+
+def _clear(m):
+    for p in m.parameters():
+        p.grad = None
+
+
+def test_block_alone_on_a_flattened_network_accumulates():
+    """A Down block of a flattened network called alone: its store adopts the
+    network's parameter buffer (hcunet_amd.flat) and its backward adds into the
+    gradients the network's backward attached.  whole + block + whole without
+    clearing equals the sum of the three contributions, each computed from a
+    cleared state; the parameters are never copied or changed."""
+    kw, shape = CONFIGS['l2']
+    m, spec, state, x = _build(kw, shape)
+    m = m.cuda()
+    xs = torch.from_numpy(x).cuda()
+    block = m.down_steps[0]
+    steps = [lambda: _weighted_backward(m(xs), 11), lambda: _weighted_backward(block(xs), 12),
+             lambda: _weighted_backward(m(xs), 11)]
+    m(xs)   # flattens
+    values = [p.detach().clone() for p in m.parameters()]
+    ptrs = [p.data_ptr() for p in m.parameters()]
+
+    def unchanged():
+        torch.cuda.synchronize()
+        return all(p.data_ptr() == q and torch.equal(p.detach(), v)
+                   for p, q, v in zip(m.parameters(), ptrs, values))
+    in_block = {id(p) for p in block.parameters()}
+    parts = []
+    for i, step in enumerate(steps):
+        _clear(m)
+        step()
+        # the block alone reaches its own parameters only
+        assert all((p.grad is not None) == (i != 1 or id(p) in in_block) for p in m.parameters())
+        parts.append([torch.zeros_like(p, dtype=torch.float64) if p.grad is None else p.grad.double()
+                      for p in m.parameters()])
+        assert unchanged()
+    _clear(m)
+    for step in steps:
+        step()
+        assert unchanged()
+    eng_flat = m.engine().flat
+    assert block._hcu_flat.flat.untyped_storage().data_ptr() == eng_flat.untyped_storage().data_ptr()
+    for p, a, b, c in zip(m.parameters(), *parts):
+        assert torch.allclose(p.grad, (a + b + c).float(), rtol=1e-5, atol=1e-7)
+
+
+def test_partially_frozen_network():
+    """out_conv frozen: its parameters keep .grad None, every other gradient is
+    bitwise the unfrozen run's; a second backward (the frozen .grad is still
+    None, so the gradients go through a temporary buffer) doubles them."""
+    kw, shape = CONFIGS['l2']
+    m, spec, state, x = _build(kw, shape)
+    m = m.cuda()
+    xs = torch.from_numpy(x).cuda()
+    _weighted_backward(m(xs), 11)
+    ref = [p.grad.clone() for p in m.parameters()]
+    _clear(m)
+    frozen = list(m.out_conv.parameters())
+    for p in frozen:
+        p.requires_grad_(False)
+    _weighted_backward(m(xs), 11)
+    torch.cuda.synchronize()
+    assert all(p.grad is None for p in frozen)
+    for p, g in zip(m.parameters(), ref):
+        if not any(p is f for f in frozen):
+            assert torch.equal(p.grad, g)
+    _weighted_backward(m(xs), 11)
+    torch.cuda.synchronize()
+    assert all(p.grad is None for p in frozen)
+    for p, g in zip(m.parameters(), ref):
+        if not any(p is f for f in frozen):
+            assert torch.allclose(p.grad, 2 * g, rtol=1e-5, atol=1e-7)
