@@ -330,6 +330,55 @@ def env_flag(name, default):
     return default if v is None or v == '' else v != '0'
 
 
+def parse_poison(v):
+    """HCU_POISON -> None or a byte 0..255: unset, '' and '0' are off, '1' is
+    0xFF, anything else two hex digits ('3f', '00')."""
+    if v is None or v in ('', '0'):
+        return None
+    if v == '1':
+        return 0xFF
+    if len(v) != 2:
+        raise ValueError("HCU_POISON must be '1' or two hex digits, got %r" % (v,))
+    return int(v, 16)
+
+
+# None, or the byte every buffer handed out by empty() is filled with.  The
+# executor never clears its device memory: a step is correct only when each
+# kernel writes every word a later kernel reads, so for the same inputs every
+# result is bitwise the same whatever this byte is (tests/test_gpu_poison.py;
+# 0xFF reads as NaN in fp32 / bf16 / fp16, 0x3F as about 0.75, which ReLU, max
+# and sign selections do not swallow).  Read once from HCU_POISON at import;
+# tests set the attribute.
+# Not routed through empty(), deliberately: buffers whose zero is part of the
+# contract (torch.zeros: Adam's M and V, FlatParams.comm at creation, the
+# 'random' loss's counts_px, the recurrent states) and the int32 buffers of
+# the 'random' loss (counts, pos_list, neg_list): indices and counts, where a
+# poisoned word would be an out-of-bounds address, not a wrong number.
+POISON = parse_poison(os.environ.get('HCU_POISON'))
+
+
+def poison(t):
+    """Fill the contiguous tensor t with the POISON byte (callers test POISON)."""
+    t.reshape(-1).view(torch.uint8).fill_(POISON)
+    return t
+
+
+def empty(shape, dtype, device):
+    """An uninitialised buffer whose contents the kernels are meant to define."""
+    t = torch.empty(shape, dtype=dtype, device=device)
+    if POISON is not None:
+        poison(t)
+    return t
+
+
+def empty_like(ref):
+    """empty() with the shape, dtype and device of `ref`, contiguous."""
+    t = torch.empty_like(ref, memory_format=torch.contiguous_format)
+    if POISON is not None:
+        poison(t)
+    return t
+
+
 def require_device(t, what):
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor, got %s" % (what, type(t)))

@@ -209,7 +209,7 @@ class _ChainPlan(_lib.Plan):
     def images_for(self, key, dev):
         """The image buffer and how much of it holds the images of `key`."""
         if self.images is None or self.images.device != dev:
-            self.images = torch.empty(max(self.image_bytes, 16), dtype=torch.uint8, device=dev)
+            self.images = _lib.empty(max(self.image_bytes, 16), torch.uint8, dev)
             self.image_key, self.image_level = None, 0
         if key != self.image_key:
             self.image_key, self.image_level = key, 0
@@ -224,14 +224,13 @@ class _ChainFunction(torch.autograd.Function):
         dev = x.device
         if chain.out_cl:
             B, C, X, Y, Z = plan.out_shape
-            out = torch.empty((B, X, Y, Z, cl_channels(C, bf16)), dtype=torch.bfloat16 if bf16 else torch.float32,
-                              device=dev)
+            out = _lib.empty((B, X, Y, Z, cl_channels(C, bf16)), torch.bfloat16 if bf16 else torch.float32, dev)
         else:
-            out = torch.empty(plan.out_shape, dtype=torch.float32, device=dev)
+            out = _lib.empty(plan.out_shape, torch.float32, dev)
         # the weight images live in the plan's persistent buffer (the end of
         # `saved` is not needed)
-        saved = torch.empty(max(plan.saved_bytes - plan.image_bytes, 1), dtype=torch.uint8, device=dev)
-        scratch = torch.empty(max(plan.scratch_bytes, 1), dtype=torch.uint8, device=dev)
+        saved = _lib.empty(max(plan.saved_bytes - plan.image_bytes, 1), torch.uint8, dev)
+        scratch = _lib.empty(max(plan.scratch_bytes, 1), torch.uint8, dev)
         t = _lib.tensors(chain.flat.flat, chain.bn, x, out, saved, scratch)
         L = _lib.lib()
         if TAG_CHAINS:
@@ -268,10 +267,10 @@ class _ChainFunction(torch.autograd.Function):
             dout = dout.contiguous().to(torch.bfloat16 if ctx.bf16 else torch.float32)
         else:
             dout = dout.contiguous().float()
-        scratch = torch.empty(max(plan.scratch_bytes, 1), dtype=torch.uint8, device=dev)
+        scratch = _lib.empty(max(plan.scratch_bytes, 1), torch.uint8, dev)
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = torch.empty(x.shape, dtype=x.dtype if chain.in_cl else torch.float32, device=dev)
+            dx = _lib.empty(x.shape, x.dtype if chain.in_cl else torch.float32, dev)
         G, accumulate, finish = chain.flat.grad_target(overwrite=False)
         t = _lib.tensors(chain.flat.flat, chain.bn, x, None, saved, scratch, grads=G)
         L = _lib.lib()

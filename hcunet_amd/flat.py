@@ -174,6 +174,8 @@ class FlatParams:
         if all(g is None for g in grads):
             if not overwrite:
                 G.zero_()
+            elif _lib.POISON is not None:
+                _lib.poison(G)   # accumulate == 0: the backward writes every trainable slot
 
             def finish():
                 for p, v, _ in rows:
@@ -185,7 +187,7 @@ class FlatParams:
                 g is not None and g.data_ptr() == base + 4 * o and g.shape == p.shape
                 for g, (p, _, o) in zip(grads, rows)):
             return G, 1, _nothing
-        tmp = torch.empty_like(flat) if overwrite else torch.zeros_like(flat)
+        tmp = _lib.empty_like(flat) if overwrite else torch.zeros_like(flat)
 
         def finish_foreign():
             for p, _, o in rows:

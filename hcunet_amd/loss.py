@@ -28,11 +28,10 @@ class _PixelBCE(torch.autograd.Function):
         dev = pred.device
         B, C, PX, PY, PZ = pred.shape
         MX, MY, MZ = mask.shape[2:]
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        dpred = torch.empty_like(pred) if pred.requires_grad else None
+        loss = _lib.empty((), torch.float32, dev)
+        dpred = _lib.empty_like(pred) if pred.requires_grad else None
         n = pred.numel()
-        scratch = torch.empty(max(_lib.lib().hcu_loss_pixel_scratch_bytes(n), 16),
-                              dtype=torch.uint8, device=dev)
+        scratch = _lib.empty(max(_lib.lib().hcu_loss_pixel_scratch_bytes(n), 16), torch.uint8, dev)
         wdt = _DTYPES[pwl.dtype] if pwl is not None else _lib.HCU_F32
         _lib.check(_lib.lib().hcu_loss_pixel_fwd(
             _lib.ptr(pred), B, C, PX, PY, PZ, _lib.ptr(mask), _DTYPES[mask.dtype], _lib.ptr(pwl),
@@ -48,7 +47,7 @@ class _PixelBCE(torch.autograd.Function):
         if dpred is None:
             return None, None, None
         grad = grad.contiguous().float()
-        out = torch.empty_like(dpred)
+        out = _lib.empty_like(dpred)
         _lib.check(_lib.lib().hcu_scale_by_device_scalar(
             _lib.ptr(dpred), _lib.ptr(grad), _lib.ptr(out), dpred.numel(),
             _lib.stream_handle(dpred.device)), 'cross_entropy backward')
@@ -74,7 +73,7 @@ class _LossExt(torch.autograd.Function):
         L = _lib.lib()
         pg, mg = _geom(pred, mask)
         n = pred.numel()
-        loss = torch.empty((), dtype=torch.float32, device=dev)
+        loss = _lib.empty((), torch.float32, dev)
         mdt = _DTYPES[mask.dtype]
         wdt = _DTYPES[pwl.dtype] if pwl is not None else _lib.HCU_F32
         counts_px = None
@@ -101,8 +100,8 @@ class _LossExt(torch.autograd.Function):
                 pos_ind = pos_ind.to(dev)
                 neg_ind = neg_ind.to(dev)
                 counts_px = torch.zeros(n, dtype=torch.int32, device=dev)
-                aux = torch.empty(1, dtype=torch.float32, device=dev)
-                scratch = torch.empty(max(16, (2 * nr + 255) // 256) * 16, dtype=torch.uint8, device=dev)
+                aux = _lib.empty(1, torch.float32, dev)
+                scratch = _lib.empty(max(16, (2 * nr + 255) // 256) * 16, torch.uint8, dev)
                 _lib.check(L.hcu_loss_random_fwd(
                     _lib.ptr(pred), *pg, _lib.ptr(mask), mdt, *mg, _lib.ptr(offs), _lib.ptr(pos_list),
                     _lib.ptr(neg_list), _lib.ptr(pos_ind), _lib.ptr(neg_ind), nr, _lib.ptr(counts_px),
@@ -110,11 +109,11 @@ class _LossExt(torch.autograd.Function):
                     'cross_entropy')
         if mode != _MODE['random']:
             PZ = pg[4]
-            aux = torch.empty(max(2, PZ), dtype=torch.float32, device=dev)
+            aux = _lib.empty(max(2, PZ), torch.float32, dev)
             zscale = None
             if mode == _MODE['worst_z']:
                 zscale = (torch.linspace(1, 2, PZ) ** 2).to(dev)   # hcat/loss.py:76
-            scratch = torch.empty(L.hcu_loss_ext_scratch_bytes(mode, n, PZ), dtype=torch.uint8, device=dev)
+            scratch = _lib.empty(L.hcu_loss_ext_scratch_bytes(mode, n, PZ), torch.uint8, dev)
             _lib.check(L.hcu_loss_ext_fwd(
                 mode, _lib.ptr(pred), *pg, _lib.ptr(mask), mdt, _lib.ptr(pwl), wdt, *mg, _lib.ptr(zscale),
                 _lib.ptr(loss), _lib.ptr(aux), _lib.ptr(scratch), scratch.numel(), stream), 'loss')
@@ -130,7 +129,7 @@ class _LossExt(torch.autograd.Function):
         if not ctx.needs_input_grad[0]:
             return None, None, None, None, None
         grad = grad.contiguous().float()
-        dpred = torch.empty_like(pred)
+        dpred = _lib.empty_like(pred)
         pg, mg = _geom(pred, mask)
         mdt, wdt = ctx.dt
         _lib.check(_lib.lib().hcu_loss_ext_bwd(

@@ -94,7 +94,7 @@ class _Gate(torch.autograd.Function):
         if zp.shape != hp.shape:
             raise RuntimeError('The size of tensor a (%s) must match the size of tensor b (%s)'
                                % (list(zp.shape), list(hp.shape)))
-        out = torch.empty_like(hp)
+        out = _lib.empty_like(hp)
         _lib.check(_lib.lib().hcu_gate_fwd(_lib.ptr(hp), _lib.ptr(zp), _lib.ptr(hprev), _lib.ptr(out),
                                            hp.numel(), _lib.stream_handle(hp.device)), 'gate')
         ctx.has_prev = hprev is not None
@@ -108,8 +108,8 @@ class _Gate(torch.autograd.Function):
         if not ctx.has_prev:
             hprev = None
         dout = dout.contiguous().float()
-        dhp, dzp = torch.empty_like(hp), torch.empty_like(zp)
-        dprev = torch.empty_like(hp) if (hprev is not None and ctx.needs_input_grad[2]) else None
+        dhp, dzp = _lib.empty_like(hp), _lib.empty_like(zp)
+        dprev = _lib.empty_like(hp) if (hprev is not None and ctx.needs_input_grad[2]) else None
         _lib.check(_lib.lib().hcu_gate_bwd(_lib.ptr(hp), _lib.ptr(zp), _lib.ptr(hprev), _lib.ptr(dout),
                                            _lib.ptr(dhp), _lib.ptr(dzp), _lib.ptr(dprev), hp.numel(),
                                            _lib.stream_handle(hp.device)), 'gate backward')
@@ -135,7 +135,7 @@ class _ClCat(torch.autograd.Function):
         parts = [p.contiguous() for p in parts]
         lead = parts[0].shape[:-1]
         widths = [p.shape[-1] for p in parts]
-        out = torch.empty(tuple(lead) + (sum(widths),), dtype=parts[0].dtype, device=parts[0].device)
+        out = _lib.empty(tuple(lead) + (sum(widths),), parts[0].dtype, parts[0].device)
         _cl_cat_call(parts, out, 0)
         ctx.lead, ctx.widths = tuple(lead), widths
         return out
@@ -144,7 +144,7 @@ class _ClCat(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         g = g.contiguous()
-        grads = [torch.empty(ctx.lead + (w,), dtype=g.dtype, device=g.device) for w in ctx.widths]
+        grads = [_lib.empty(ctx.lead + (w,), g.dtype, g.device) for w in ctx.widths]
         _cl_cat_call(grads, g, 1)
         return tuple(grads)
 
@@ -169,8 +169,8 @@ class _Resid(torch.autograd.Function):
     @staticmethod
     def forward(ctx, m, y):
         m, y = m.contiguous(), y.contiguous()
-        out = torch.empty(y.shape, dtype=torch.float32, device=y.device)
-        outc = torch.empty(y.shape, dtype=m.dtype, device=y.device)
+        out = _lib.empty(y.shape, torch.float32, y.device)
+        outc = _lib.empty(y.shape, m.dtype, y.device)
         _lib.check(_lib.lib().hcu_resid_fwd(_lib.ptr(m), _lib.ptr(y), _lib.ptr(out), _lib.ptr(outc), y.numel(),
                                             _lib.stream_handle(y.device)), 'residual add')
         ctx.set_materialize_grads(False)
@@ -184,8 +184,8 @@ class _Resid(torch.autograd.Function):
         ref = g32 if g32 is not None else gc
         g32 = g32.contiguous().float() if g32 is not None else None
         gc = gc.contiguous().to(torch.bfloat16) if gc is not None else None
-        dy = torch.empty(ref.shape, dtype=torch.float32, device=ref.device)
-        dm = torch.empty(ref.shape, dtype=torch.bfloat16, device=ref.device)
+        dy = _lib.empty(ref.shape, torch.float32, ref.device)
+        dm = _lib.empty(ref.shape, torch.bfloat16, ref.device)
         _lib.check(_lib.lib().hcu_resid_bwd(_lib.ptr(g32), _lib.ptr(gc), _lib.ptr(dy), _lib.ptr(dm), dy.numel(),
                                             _lib.stream_handle(dy.device)), 'residual add backward')
         return dm, dy
@@ -206,7 +206,7 @@ class _PwConv(torch.autograd.Function):
         nvox = p0.numel() // p0.shape[-1]
         cout = conv.out_channels
         ocs = cl_channels(cout, True)
-        out = torch.empty(tuple(p0.shape[:-1]) + (ocs,), dtype=torch.bfloat16, device=p0.device)
+        out = _lib.empty(tuple(p0.shape[:-1]) + (ocs,), torch.bfloat16, p0.device)
         ptrs = (ctypes.c_void_p * len(parts))(*[p.data_ptr() for p in parts])
         _lib.check(_lib.lib().hcu_pw_conv_forward(ptrs, len(parts), part_c, p0.shape[-1], _lib.ptr(conv.weight),
                                                   _lib.ptr(conv.bias), _lib.ptr(out), nvox, cout, ocs,
@@ -232,13 +232,13 @@ class _PwConv(torch.autograd.Function):
         ocs = dout.shape[-1]
         L = _lib.lib()
         need = any(ctx.needs_input_grad[4:])
-        dparts = [torch.empty_like(p) for p in parts] if need else None
+        dparts = [_lib.empty_like(p) for p in parts] if need else None
         G, _, finish = flat.grad_target(overwrite=False)
         base = G.data_ptr()
         dw = ctypes.c_void_p(base + 4 * flat.offset(conv.weight))
         db = ctypes.c_void_p(base + 4 * flat.offset(conv.bias)) if conv.bias is not None else ctypes.c_void_p()
         nw = int(L.hcu_pw_conv_work_floats(nvox, len(parts), p0.shape[-1], cout))
-        work = torch.empty(max(nw, 1), dtype=torch.float32, device=dev)
+        work = _lib.empty(max(nw, 1), torch.float32, dev)
         ptrs = (ctypes.c_void_p * len(parts))(*[p.data_ptr() for p in parts])
         dptrs = (ctypes.c_void_p * len(parts))(*[d.data_ptr() for d in dparts]) if need else None
         _lib.check(L.hcu_pw_conv_backward(ptrs, len(parts), ctx.part_c, p0.shape[-1], _lib.ptr(conv.weight),
@@ -302,7 +302,7 @@ class _Fan(torch.autograd.Function):
         if ref.dtype not in (torch.bfloat16, torch.float32) or any(g.dtype != ref.dtype for g in live):
             return sum(live[1:], live[0]), None
         gs = [g.contiguous() if g is not None else None for g in gs]
-        out = torch.empty(ref.shape, dtype=ref.dtype, device=ref.device)
+        out = _lib.empty(ref.shape, ref.dtype, ref.device)
         ptrs = (ctypes.c_void_p * len(gs))(*[g.data_ptr() if g is not None else None for g in gs])
         _lib.check(_lib.lib().hcu_sum_parts(ptrs, len(gs), _lib.ptr(out), out.numel(),
                                             1 if ref.dtype == torch.bfloat16 else 0,

@@ -135,7 +135,7 @@ def pad_image_with_reflections(image, pad_size=(30, 30, 6)):
     B, C, X, Y, Z = vol.shape
     pads = [min(int(p), n) for p, n in zip(pad_size, (X, Y, Z))]
     dims = [n + 2 * p for n, p in zip((X, Y, Z), pads)]
-    out = torch.empty((B, C) + tuple(dims), dtype=torch.float32, device=dev)
+    out = _lib.empty((B, C) + tuple(dims), torch.float32, dev)
     _gather(vol, pads, [(0, 0, 0)], dims, False, out, _lib.stream_handle(dev))
     out = out.to(vol.dtype)
     return out if image.device == dev else out.to(image.device)
@@ -224,7 +224,7 @@ def predict_segmentation_mask(unet, image, device=None, use_probability_map=Fals
             while j < len(tiles) and j - i < cap and tiles[j][1] == tdims:
                 j += 1
             batch = tiles[i:j]
-            xb = torch.empty((len(batch), C) + tuple(tdims), dtype=torch.float32, device=dev)
+            xb = _lib.empty((len(batch), C) + tuple(tdims), torch.float32, dev)
             _gather(vol, pads, [t[0] for t in batch], tdims, True, xb, stream)
             # "Occasionally everything is just -1 in the whole mat. Skip for speed"
             skip = (xb == -1).flatten(1).all(1).tolist()

@@ -212,9 +212,9 @@ def materialise(v, device=None):
         raise ValueError(f'Expected a [Z,Y,X,C] or [Y,X,C] stack, got shape {tuple(raw.shape)}')
     Z, Y, X, C = shp
     if v.reshaped:
-        out = torch.empty((1, C, X, Y, Z), dtype=torch.float16, device=device)
+        out = _lib.empty((1, C, X, Y, Z), torch.float16, device)
     else:
-        out = torch.empty((1, C, Z, Y, X), dtype=torch.float16, device=device)
+        out = _lib.empty((1, C, Z, Y, X), torch.float16, device)
     mean = std = None
     if v.mean is not None:
         mean = (ctypes.c_double * C)(*v.mean)
@@ -242,7 +242,7 @@ def ingest(raw, mean=None, std=None, device=None):
     if code is None:
         raise TypeError('Expected image datatype of uint8 or uint16 ')
     B, Z, Y, X, C = t.shape
-    out = torch.empty((B, C, X, Y, Z), dtype=torch.float16, device=device)
+    out = _lib.empty((B, C, X, Y, Z), torch.float16, device)
     m = s = None
     if mean is not None:
         m = (ctypes.c_double * C)(*[float(x) for x in mean[:C]])

@@ -26,7 +26,6 @@ grad_target).
 """
 import ctypes
 import glob
-import os
 
 import torch
 import torch.nn as nn
@@ -422,9 +421,6 @@ class _Engine:
         return p
 
 
-_POISON = os.environ.get('HCU_POISON') == '1'
-
-
 class _NoCtx:
     def __enter__(self):
         return None
@@ -448,12 +444,9 @@ class _UnetFunction(torch.autograd.Function):
         x = x.contiguous()
         plan = eng.plan(x.shape, bf16, forward_only=fwd_only)
         dev = x.device
-        out = torch.empty(plan.out_shape, dtype=torch.float32, device=dev)
-        saved = torch.empty(max(plan.saved_bytes, 1), dtype=torch.uint8, device=dev)
-        scratch = torch.empty(max(plan.scratch_bytes, 1), dtype=torch.uint8, device=dev)
-        if _POISON:   # debugging: every byte the step does not write reads as NaN
-            saved.fill_(255)
-            scratch.fill_(255)
+        out = _lib.empty(plan.out_shape, torch.float32, dev)
+        saved = _lib.empty(max(plan.saved_bytes, 1), torch.uint8, dev)
+        scratch = _lib.empty(max(plan.scratch_bytes, 1), torch.uint8, dev)
         training = 1 if eng.module_ref.training else 0
         t = _lib.tensors(eng.flat, eng.bn, x, out, saved, scratch)
         # The executor's graph-capture and side streams are created on the
@@ -478,10 +471,8 @@ class _UnetFunction(torch.autograd.Function):
         dout = dout.contiguous()
         if dout.dtype != torch.float32:
             dout = dout.float()
-        scratch = torch.empty(max(plan.scratch_bytes, 1), dtype=torch.uint8, device=dev)
-        if _POISON:
-            scratch.fill_(255)
-        dx = torch.empty(x.shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        scratch = _lib.empty(max(plan.scratch_bytes, 1), torch.uint8, dev)
+        dx = _lib.empty(x.shape, torch.float32, dev) if ctx.needs_input_grad[0] else None
         G, accumulate, finish = eng.grad_target()
         t = _lib.tensors(eng.flat, eng.bn, x, None, saved, scratch, grads=G)
         ev = eng.grad_events if G is eng.grad_flat else None

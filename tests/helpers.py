@@ -46,8 +46,10 @@ def out_dims(d):
 
 
 def scratch_for(d):
+    """The op's scratch workspace, every byte 0xFF (NaN as fp32 / bf16): an op
+    must write each scratch word it reads (tests/test_gpu_poison.py)."""
     n = _lib.lib().hcu_conv_scratch_bytes(ctypes.byref(d))
-    return torch.empty(max(n, 16), dtype=torch.uint8, device='cuda')
+    return torch.full((max(n, 16),), 0xFF, dtype=torch.uint8, device='cuda')
 
 
 def stream():

@@ -377,12 +377,14 @@ def test_chain_weight_images_follow_parameter_updates():
 @pytest.mark.parametrize('dtype,widths', [
     (dt, w) for dt in (torch.bfloat16, torch.float32) for w in ((16, 16), (16, 16, 16, 16, 16))] + [
     (torch.float32, (8, 24, 4, 4)), (torch.bfloat16, (8, 24, 8, 16))])
-def test_channel_cat_matches_torch_cat(dtype, widths):
+def test_channel_cat_matches_torch_cat(dtype, widths, monkeypatch):
     """hcu_cl_cat (RDCNet's recurrence cats, hcat/r_unet.py:223,362): forward
     bitwise equal to torch.cat(dim=-1), and each part's gradient bitwise
     equal to torch.cat's backward (contiguous tensors here; rows of 16-byte
-    multiples, narrow parts included)."""
+    multiples, narrow parts included), into NaN-prefilled outputs."""
+    from hcunet_amd import _lib
     from hcunet_amd.r_unet import cl_cat
+    monkeypatch.setattr(_lib, 'POISON', 0xFF)
     vec = 16 // torch.empty(0, dtype=dtype).element_size()
     assert all(w % vec == 0 for w in widths)
     dev = torch.device('cuda', 0)
@@ -401,12 +403,14 @@ def test_channel_cat_matches_torch_cat(dtype, widths):
 
 
 @pytest.mark.parametrize('use', ['both', 'cast', 'fp32'])
-def test_residual_add_matches_torch(use):
+def test_residual_add_matches_torch(use, monkeypatch):
     """hcu_resid_fwd/bwd (RDCNet's residual under autocast, hcat/r_unet.py
     :223-225): m (bf16) + y (fp32) and its bf16 cast bitwise equal to torch's
     promoting add and .to(), and so are the gradients of m and y with either
-    or both outputs used."""
+    or both outputs used; every output NaN-prefilled."""
+    from hcunet_amd import _lib
     from hcunet_amd.r_unet import resid_add
+    monkeypatch.setattr(_lib, 'POISON', 0xFF)
     dev = torch.device('cuda', 0)
     g = torch.Generator(device='cpu').manual_seed(11)
     m = torch.randn(1, 33, 21, 13, 16, generator=g).to(torch.bfloat16).to(dev).requires_grad_()
@@ -432,11 +436,13 @@ def test_residual_add_matches_torch(use):
 
 
 @pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float32])
-def test_fan_gradient_sum(dtype):
+def test_fan_gradient_sum(dtype, monkeypatch):
     """hcu_sum_parts behind fan(): the k consumers' gradients summed in fp32
     in consumer order and rounded once (bitwise equal to that sum in torch),
-    unused consumers skipped."""
+    unused consumers skipped; the sum goes into a NaN-prefilled output."""
+    from hcunet_amd import _lib
     from hcunet_amd.r_unet import fan
+    monkeypatch.setattr(_lib, 'POISON', 0xFF)
     dev = torch.device('cuda', 0)
     g = torch.Generator(device='cpu').manual_seed(5)
     t = torch.randn(1, 17, 19, 13, 16, generator=g).to(dtype).to(dev).requires_grad_()
@@ -562,18 +568,19 @@ def test_pw_conv_c_abi_matches_torch(nparts, part_c, cout, nvox):
     db = dy.double().sum(0)
     pad = lambda t, c: torch.nn.functional.pad(t, (0, c - t.shape[1])).to(torch.bfloat16).to(dev).contiguous()  # noqa: E731
     parts = [pad(t, pcs) for t in xs]
-    out = torch.empty(nvox, ocs, dtype=torch.bfloat16, device=dev)
+    nan = float('nan')   # every output and workspace prefilled: each word must be written
+    out = torch.full((nvox, ocs), nan, dtype=torch.bfloat16, device=dev)
     L = _lib.lib()
     ptrs = (ctypes.c_void_p * nparts)(*[p.data_ptr() for p in parts])
     wd, bd = w.to(dev), b.to(dev)
     st = _lib.stream_handle(dev)
     _lib.check(L.hcu_pw_conv_forward(ptrs, nparts, part_c, pcs, _lib.ptr(wd), _lib.ptr(bd), _lib.ptr(out),
                                      nvox, cout, ocs, st), 'pw forward')
-    dparts = [torch.full_like(p, 7.0) for p in parts]
+    dparts = [torch.full_like(p, nan) for p in parts]
     dptrs = (ctypes.c_void_p * nparts)(*[d.data_ptr() for d in dparts])
     gw, gb = torch.ones(cout, cin, device=dev), torch.ones(cout, device=dev)   # accumulated onto
     nw = int(L.hcu_pw_conv_work_floats(nvox, nparts, pcs, cout))
-    work = torch.empty(max(nw, 1), device=dev)
+    work = torch.full((max(nw, 1),), nan, device=dev)
     _lib.check(L.hcu_pw_conv_backward(ptrs, nparts, part_c, pcs, _lib.ptr(wd), _lib.ptr(pad(dy, ocs)), cout, ocs,
                                       dptrs, _lib.ptr(gw), _lib.ptr(gb), nvox, _lib.ptr(work), nw, 1, st),
                'pw backward')

@@ -238,3 +238,51 @@ def test_bench_dump_outputs_snapshot(tmp_path):
     bench.write_dump(str(tmp_path / 'd'), s1)
     for k, a in s1.items():
         np.testing.assert_array_equal(np.load(str(tmp_path / 'd' / (k + '.npy'))), a)
+
+
+def test_poison_hook_on_host_tensors(monkeypatch):
+    """hcunet_amd._lib.empty / empty_like / FlatParams.grad_target under
+    _lib.POISON, and HCU_POISON's parsing: unset, '' and '0' off, '1' 0xFF,
+    otherwise two hex digits."""
+    from hcunet_amd.flat import FlatParams
+    assert _lib.parse_poison(None) is None and _lib.parse_poison('') is None
+    assert _lib.parse_poison('0') is None
+    assert _lib.parse_poison('1') == 0xFF
+    assert _lib.parse_poison('3f') == 0x3F and _lib.parse_poison('FF') == 0xFF
+    assert _lib.parse_poison('00') == 0
+    for bad in ('2', 'zz', '3f3f'):
+        with pytest.raises(ValueError):
+            _lib.parse_poison(bad)
+    cpu = torch.device('cpu')
+    monkeypatch.setattr(_lib, 'POISON', 0x3F)
+    for dtype, shape in ((torch.float32, (3, 5)), (torch.bfloat16, (7,)), (torch.float16, (2, 3)),
+                         (torch.uint8, (9,)), (torch.float32, ()), (torch.float32, (0, 4))):
+        t = _lib.empty(shape, dtype, cpu)
+        assert t.shape == torch.Size(shape) and t.dtype == dtype
+        assert (t.reshape(-1).view(torch.uint8) == 0x3F).all()
+    ref = torch.zeros(4, 6).t()   # not contiguous: the like is
+    t = _lib.empty_like(ref)
+    assert t.shape == ref.shape and t.is_contiguous() and (t.reshape(-1).view(torch.uint8) == 0x3F).all()
+    monkeypatch.setattr(_lib, 'POISON', 0xFF)
+    assert torch.isnan(_lib.empty((4,), torch.float32, cpu)).all()
+    assert torch.isnan(_lib.empty((4,), torch.bfloat16, cpu)).all()
+    assert torch.isnan(_lib.empty((4,), torch.float16, cpu)).all()
+    # the gradient target: poisoned where the backward overwrites (accumulate
+    # == 0), zero where it adds, the statistics tail (comm, torch.zeros) untouched
+    for overwrite in (True, False):
+        store = FlatParams(torch.nn.Linear(3, 2)).ready(require_gpu=False)
+        store.stats_tail = 4
+        G, accumulate, _ = store.grad_target(overwrite=overwrite)
+        assert accumulate == (0 if overwrite else 1)
+        assert bool(torch.isnan(G).all()) == overwrite and (overwrite or not G.any())
+        assert not store.comm[G.numel():].any()
+    # unset: no fill (the buffer is whatever the allocator returned; the hook
+    # must not touch it -- a fill would show as a write into a tensor that
+    # shares the storage)
+    monkeypatch.setattr(_lib, 'POISON', None)
+    calls = []
+    monkeypatch.setattr(_lib, 'poison', lambda t: calls.append(t))
+    _lib.empty((8,), torch.float32, cpu)
+    _lib.empty_like(ref)
+    FlatParams(torch.nn.Linear(3, 2)).ready(require_gpu=False).grad_target(overwrite=True)
+    assert not calls
