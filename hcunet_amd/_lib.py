@@ -160,6 +160,34 @@ class BNLayerInfo(ctypes.Structure):
     ]
 
 
+INGEST_MAX_C = 16
+AUG_MAX_STEPS = 8
+AUG_NORMALIZE, AUG_INTENSITY, AUG_DROP, AUG_CLEAN, AUG_GAMMA, AUG_SPEKLE = 1, 2, 3, 4, 5, 6
+
+
+class AugStep(ctypes.Structure):
+    _fields_ = [
+        ("kind", ctypes.c_int), ("key", ctypes.c_uint),
+        ("a", ctypes.c_double * INGEST_MAX_C), ("b", ctypes.c_double * INGEST_MAX_C),
+    ]
+
+
+class IngestJob(ctypes.Structure):
+    _fields_ = [
+        ("src", ctypes.c_void_p), ("dst", ctypes.c_void_p),
+        ("xmap_dev", ctypes.c_void_p), ("ymap_dev", ctypes.c_void_p),
+        ("xmap_host", ctypes.c_void_p), ("ymap_host", ctypes.c_void_p),
+        ("src_dtype", ctypes.c_int), ("Z", ctypes.c_int), ("Y", ctypes.c_int), ("X", ctypes.c_int),
+        ("C", ctypes.c_int),
+        ("ox", ctypes.c_int), ("oy", ctypes.c_int), ("oz", ctypes.c_int),
+        ("x0", ctypes.c_int), ("y0", ctypes.c_int), ("z0", ctypes.c_int),
+        ("n_chan", ctypes.c_int), ("chan", ctypes.c_int * INGEST_MAX_C),
+        ("n_steps", ctypes.c_int),
+        ("scale", ctypes.c_double),
+        ("steps", AugStep * AUG_MAX_STEPS),
+    ]
+
+
 # Every symbol include/hcunet.h declares: (name, restype, argtypes)
 _VP, _I, _I64, _F, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 SYMBOLS = [
@@ -189,6 +217,7 @@ SYMBOLS = [
                                  _I, _VP, _VP, _VP, _VP, _SZ, _VP]),
     ("hcu_ingest_volume", _I, [_VP, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_double),
                                ctypes.POINTER(ctypes.c_double), _VP, _VP]),
+    ("hcu_ingest_jobs", _I, [_VP, _VP, _I, _VP]),
     ("hcu_adam_step", _I, [_VP, _VP, _VP, _VP, _I64, _F, _F, _F, _F, _F, _I64, _F, _VP]),
     ("hcu_conv_scratch_bytes", _SZ, [ctypes.POINTER(ConvDesc)]),
     ("hcu_conv_out_dims", _I, [ctypes.POINTER(ConvDesc), ctypes.POINTER(_I)]),

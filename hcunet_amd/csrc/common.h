@@ -94,6 +94,27 @@ __device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
                     pack_bf2(f[6], f[7]));
 }
 
+// float64 -> fp16 bits, round to nearest even (overflow -> inf, NaN kept).
+__device__ __forceinline__ uint16_t d2h_rne(double d) {
+  const uint64_t b = (uint64_t)__double_as_longlong(d);
+  const uint32_t sign = (uint32_t)(b >> 48) & 0x8000u;
+  const int e = (int)((b >> 52) & 0x7ff);
+  const uint64_t mant = b & 0xFFFFFFFFFFFFFull;
+  if (e == 0x7ff) return (uint16_t)(sign | 0x7c00u | (mant ? 0x200u : 0u));
+  const int ex = e - 1023;
+  if (ex > 15) return (uint16_t)(sign | 0x7c00u);
+  if (ex < -25) return (uint16_t)sign;   // below half the smallest subnormal
+  const uint64_t m = mant | (1ull << 52);
+  const int shift = ex >= -14 ? 42 : 42 + (-14 - ex);
+  uint64_t q = m >> shift;
+  const uint64_t rem = m & ((1ull << shift) - 1), halfw = 1ull << (shift - 1);
+  if (rem > halfw || (rem == halfw && (q & 1))) ++q;
+  uint32_t h;
+  if (ex >= -14) h = ((uint32_t)(ex + 15) << 10) + (uint32_t)(q - 1024);   // q == 2048 carries
+  else h = (uint32_t)q;                                                     // subnormal (or carry to min normal)
+  return (uint16_t)(sign | h);
+}
+
 inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 

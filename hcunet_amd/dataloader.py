@@ -10,7 +10,14 @@ errors and __getitem__ order of transforms as the reference.  What changes:
   and returns fp16 tensors already on the GPU;
 * `prefetch(order)` yields items while the next one is copied and converted
   on a side stream (the reference converts on the host and copies float
-  tensors, segment.py:89 / the training loop's .cuda()).
+  tensors, segment.py:89 / the training loop's .cuda());
+* `resident_bytes=` keeps the raw stacks in HBM after their first use, so a
+  random crop reads its window from device memory instead of copying the
+  whole stack per item;
+* `batches(batch_size)` yields fp16 (image, mask, pwl) batches [B,C,X,Y,Z]:
+  the transform lists run per item (recording crops and augmentations, with
+  the reference's RNG draws in item order) and all volumes of a batch are
+  converted by one hcu_ingest_jobs launch on a side stream.
 Files are read with skimage.io.imread (as the reference) or tifffile when
 importable; `reader=` takes any callable path -> ndarray.
 """
@@ -20,6 +27,7 @@ import os
 import numpy as np
 import torch
 
+from . import _lib
 from . import transforms as t
 
 
@@ -52,15 +60,35 @@ class _Raw:
     for expand_dims / ndim / dtype purposes and hands the pinned tensor to the
     device path."""
 
-    def __init__(self, a):
+    def __init__(self, a, stack=None):
         self.tensor, self.np_dtype, _ = _pinned(a)
+        self.stack = stack
+        self.keep_lists = {}    # nul_crop's keep lists of the uncropped mask (it never changes)
+        self.device_copy = {}   # device -> (resident raw tensor, event of its upload)
 
     def pending(self, expand=False):
         r = self.tensor.unsqueeze(self.tensor.dim()) if expand else self.tensor
-        return t.PendingVolume(r, np_dtype=self.np_dtype)
+        return t.PendingVolume(r, np_dtype=self.np_dtype, source=self)
+
+    def resident(self, device):
+        """The raw stack in HBM, uploaded on first use and kept while the
+        Stack's resident_bytes budget lasts; None: copy this item as it comes."""
+        hit = self.device_copy.get(device)
+        if hit is None:
+            nbytes = self.tensor.numel() * self.tensor.element_size()
+            if self.stack is None or not self.stack._reserve(nbytes):
+                return None
+            d = self.tensor.to(device, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(device))
+            hit = self.device_copy[device] = (d, ev)
+        d, ev = hit
+        torch.cuda.current_stream(device).wait_event(ev)   # (an upload on another stream)
+        return d
 
 
-_LAZY = (t.to_float, t.reshape, t.normalize, t.to_tensor)
+_LAZY = (t.to_float, t.reshape, t.normalize, t.to_tensor, t.random_crop, t.nul_crop, t.random_intensity,
+         t.drop_channel, t.clean_image, t.remove_channel, t.random_gamma, t.spekle)
 
 
 def _arrays_for(transform, items):
@@ -75,7 +103,11 @@ def _arrays_for(transform, items):
 class Stack(torch.utils.data.Dataset):
     """Dataloader for hcat.unet: 3D stacks with mask and pixel-weight maps."""
 
-    def __init__(self, path, image_transforms, joint_transforms, out_transforms=None, reader=None):
+    def __init__(self, path, image_transforms, joint_transforms, out_transforms=None, reader=None,
+                 resident_bytes=None):
+        # raw bytes kept in HBM after their first use: None all stacks, 0 none
+        # (every item copies its stacks); stacks beyond the budget are copied per item
+        self.resident_left = float('inf') if resident_bytes is None else int(resident_bytes)
         if out_transforms is None:
             out_transforms = [t.to_tensor()]
         self.image_transforms = image_transforms
@@ -93,19 +125,26 @@ class Stack(torch.utils.data.Dataset):
             file_with_mask = os.path.splitext(mask_path)[0]
             image_data_path = os.path.splitext(file_with_mask)[0] + '.tif'
             pwl_data_path = os.path.splitext(file_with_mask)[0] + '.pwl.tif'
-            self.image.append(_Raw(reader(image_data_path)))
+            self.image.append(_Raw(reader(image_data_path), self))
             m = reader(mask_path)
             try:   # some masks are [Z,Y,X,C], others [Z,Y,X] (:57-61)
                 m = m[:, :, :, 0]
             except IndexError:
                 pass
-            self.mask.append(_Raw(m))
-            self.pwl.append(_Raw(reader(pwl_data_path)))
+            self.mask.append(_Raw(m, self))
+            self.pwl.append(_Raw(reader(pwl_data_path), self))
 
     def __len__(self):
         return len(self.files)
 
-    def __getitem__(self, item):
+    def _reserve(self, nbytes):
+        if nbytes > self.resident_left:
+            return False
+        self.resident_left -= nbytes
+        return True
+
+    def _recorded(self, item):
+        """The joint and image transforms of one item (:79-86)."""
         # channel axis last (:80-81), on the pinned raw tensors (no copy)
         image = self.image[item].pending()
         mask = self.mask[item].pending(expand=True)
@@ -116,6 +155,10 @@ class Stack(torch.utils.data.Dataset):
         for it in self.image_transforms:
             image = _arrays_for(it, [image])[0]
             image = it(image)
+        return image, mask, pwl
+
+    def __getitem__(self, item):
+        image, mask, pwl = self._recorded(item)
         for ot in self.out_transforms:
             image, mask, pwl = _arrays_for(ot, [image, mask, pwl])
             image, mask, pwl = ot([image, mask, pwl])
@@ -146,3 +189,54 @@ class Stack(torch.utils.data.Dataset):
                 if isinstance(x, torch.Tensor):
                     x.record_stream(main)
             yield items
+
+    def _batch(self, items, device):
+        """fp16 (image [B,C,X,Y,Z], mask, pwl) of the items, one launch."""
+        vols = []
+        for i in items:   # RNG draws in item order, to_tensor's joint seed included: the stream of self[i]
+            vols.append([t._wrap(x) for x in self._recorded(i)])
+            np.random.randint(0, 1e8, 1)
+        outs = []
+        for k in range(3):
+            shapes = [v[k].shape for v in vols]
+            if any(len(s) != 4 for s in shapes):
+                raise ValueError(f'Stack.batches expects [x,y,z,c] volumes, got {shapes} for items {items}')
+            if len(set(shapes)) != 1:
+                raise ValueError('Stack.batches: the items of one batch end with different extents: '
+                                 + ', '.join(f'item {i}: {s}' for i, s in zip(items, shapes)))
+            X, Y, Z, C = shapes[0]
+            outs.append(_lib.empty((len(items), C, X, Y, Z), torch.float16, device))
+        flat = [v[k] for v in vols for k in range(3)]
+        t.materialise_many(flat, [outs[k][b] for b in range(len(items)) for k in range(3)], device)
+        return tuple(outs)
+
+    def batches(self, batch_size, order=None, device=None):
+        """Yield fp16 (image [B,C,X,Y,Z], mask [B,1,X,Y,Z], pwl [B,1,X,Y,Z]) on
+        the device for consecutive groups of `batch_size` items of `order`
+        (a short last batch as it is).  The joint and image transform lists run
+        per item; every volume of a batch is a job of one launch (the device
+        pass replaces out_transforms); batch k+1 is prepared on a side stream
+        while batch k is consumed, as in `prefetch`.  ValueError when the items
+        of a batch end with different extents."""
+        order = list(range(len(self))) if order is None else list(order)
+        device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        groups = [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+        side = torch.cuda.Stream(device)
+        main = torch.cuda.current_stream(device)
+
+        def launch(items):
+            with torch.cuda.stream(side):
+                out = self._batch(items, device)
+            ev = torch.cuda.Event()
+            ev.record(side)
+            return out, ev
+
+        nxt = launch(groups[0]) if groups else None
+        for k in range(len(groups)):
+            out, ev = nxt
+            if k + 1 < len(groups):
+                nxt = launch(groups[k + 1])
+            main.wait_event(ev)
+            for x in out:
+                x.record_stream(main)
+            yield out

@@ -388,7 +388,69 @@ int hcu_ingest_volume(const void *src, int src_dtype, int B, int Z, int Y, int X
                       void *dst, hcu_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
-/* Optimizer.  Replaces torch.optim.Adam.step (tests/r_unet_test.py:24,56)   */
+/* Input path with crops and augmentation: n_jobs independent volumes in ONE */
+/* launch (the image, mask and pixel-weight map of every item of a batch).   */
+/* A job reads a window of a raw stack src [Z][Y][X][C] (HCU_U16 / HCU_U8)   */
+/* and writes the network input dst [n_chan][ox][oy][oz] fp16, i.e. the      */
+/* reference's to_float (hcat/transforms.py:94-116) -> reshape (:139-157) -> */
+/* crops -> per-voxel steps -> to_tensor (:118-137) chain:                   */
+/*   window   output (i, j, k) reads source x = xmap ? xmap[i] : x0 + i,     */
+/*            y = ymap ? ymap[j] : y0 + j, z = z0 + k: random_crop's window  */
+/*            (:337-396) composed with nul_crop's keep lists (:460-489);     */
+/*   channels output channel c reads source channel chan[c]                  */
+/*            (remove_channel, :590-613);                                    */
+/*   steps    v = src * scale, then the program in recorded order, float64,  */
+/*            a / b the operands of output channel c:                        */
+/*     HCU_AUG_NORMALIZE  v = (v + -a) / b                  normalize :257-283 */
+/*     HCU_AUG_INTENSITY  v -= a; v<0 -> 0, NaN -> 0, Inf -> 1              */
+/*                                                   random_intensity :301-334 */
+/*     HCU_AUG_DROP       a != 0: v = 0                  drop_channel :285-298 */
+/*     HCU_AUG_CLEAN      NaN -> 0, +-Inf -> 1            clean_image :616-631 */
+/*     HCU_AUG_GAMMA      v = pow(v, a), v >= 0          random_gamma :186-197 */
+/*     HCU_AUG_SPEKLE     v += (float)(a * n), then v<0 -> 0, v>1 -> 1, n a   */
+/*                        standard normal (Philox-4x32-10 keyed by key, the   */
+/*                        job and step index, the output voxel and the channel */
+/*                        pair; Box-Muller in float64, cosine branch for the   */
+/*                        even channel, sine for the odd): the distribution of */
+/*                        spekle (:159-183), not numpy's stream;               */
+/*   rounding float64 -> float32 -> fp16, each to nearest even (torch's).     */
+/* jobs_host is the table in host memory, jobs_dev the caller's copy of it in */
+/* device memory (copied on `stream` before the call); xmap_host / ymap_host  */
+/* are the host copies of the device maps.  Nothing is allocated.  Every job  */
+/* is validated on the host BEFORE anything is enqueued: a window or a map    */
+/* entry outside the source, or an empty extent, is HCU_ERR_SHAPE; more than  */
+/* HCU_INGEST_MAX_C channels, more than HCU_AUG_MAX_STEPS steps, or a source  */
+/* or destination of 2^31 bytes / elements or more, HCU_ERR_UNSUPPORTED;      */
+/* other dtypes, step kinds, channel indices and null pointers                */
+/* HCU_ERR_INVALID.                                                           */
+/* ------------------------------------------------------------------------ */
+#define HCU_INGEST_MAX_C 16
+#define HCU_AUG_MAX_STEPS 8
+enum { HCU_AUG_NORMALIZE = 1, HCU_AUG_INTENSITY = 2, HCU_AUG_DROP = 3, HCU_AUG_CLEAN = 4,
+       HCU_AUG_GAMMA = 5, HCU_AUG_SPEKLE = 6 };
+typedef struct hcu_aug_step {
+  int kind;
+  unsigned int key;                  /* HCU_AUG_SPEKLE: the noise key */
+  double a[HCU_INGEST_MAX_C], b[HCU_INGEST_MAX_C];
+} hcu_aug_step;
+typedef struct hcu_ingest_job {
+  const void *src;                   /* device, [Z][Y][X][C] of src_dtype */
+  void *dst;                         /* device, fp16 [n_chan][ox][oy][oz] */
+  const int *xmap_dev, *ymap_dev;    /* device int32 [ox] / [oy], or null: origin */
+  const int *xmap_host, *ymap_host;  /* the same entries in host memory */
+  int src_dtype, Z, Y, X, C;
+  int ox, oy, oz;                    /* output extent along the source's x, y, z */
+  int x0, y0, z0;                    /* window origin (x0 / y0 unused with a map) */
+  int n_chan, chan[HCU_INGEST_MAX_C];
+  int n_steps;
+  double scale;                      /* to_float: 2^-16, 2^-8, or 1 */
+  hcu_aug_step steps[HCU_AUG_MAX_STEPS];
+} hcu_ingest_job;
+int hcu_ingest_jobs(const hcu_ingest_job *jobs_host, const hcu_ingest_job *jobs_dev, int n_jobs,
+                    hcu_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* Optimizer. Replaces torch.optim.Adam.step (tests/r_unet_test.py:24,56)   */
 /* for a flat parameter buffer: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;  */
 /* p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps); L2 weight decay.     */
 /* ------------------------------------------------------------------------ */
