@@ -185,6 +185,12 @@ class IngestJob(ctypes.Structure):
         ("n_steps", ctypes.c_int),
         ("scale", ctypes.c_double),
         ("steps", AugStep * AUG_MAX_STEPS),
+        # random_rotate; a zero-filled record means "no rotation"
+        ("rot", ctypes.c_int),
+        ("rot_m", ctypes.c_double * 4), ("rot_off", ctypes.c_double * 2),
+        ("rot_nx", ctypes.c_int), ("rot_ny", ctypes.c_int),
+        ("rot_px", ctypes.c_int), ("rot_py", ctypes.c_int),
+        ("fill_after", ctypes.c_int),
     ]
 
 

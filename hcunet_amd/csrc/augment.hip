@@ -9,6 +9,17 @@
 // :159-183) and rounds as torch does (float64 -> float32 -> fp16), writing
 // [C'][ox][oy][oz] fp16.
 //
+// random_rotate (:230-254) is an addressing mode of the load phase, not a pass
+// of its own: with J.rot the window / maps describe the pre-rotation view and
+// every output (x, y) gathers its nearest source voxel of that view, exactly as
+// scipy.ndimage.rotate(order=0, mode='constant', reshape=False) picks it --
+// float64 coordinates with every product and sum rounded on its own (fused
+// multiply-adds move the .5 ties), computed once per tile column and reused
+// for its z rows.  A voxel whose source lies outside issues no load, starts
+// from 0.0 at step J.fill_after and runs the steps that were recorded after
+// the rotation.  Neighbouring output rows reuse the same source cache lines,
+// so the gather goes through L2 / the vector cache, not through LDS.
+//
 // A workgroup owns a tile of 32 x by ty y by tz z output voxels of one job
 // (all its channels), staged in LDS: the reads run along (x, c), the source's
 // contiguous direction, and the writes along (y, z), the destination's -- a
@@ -18,6 +29,7 @@
 #include "common.h"
 #include "timing.h"
 #include "hcunet.h"
+#include <cmath>
 #include <cstring>
 
 namespace hcu {
@@ -113,7 +125,29 @@ __device__ __forceinline__ uint32_t aug_elem(const uint32_t (&w)[4], int k) {
   return (d >> ((bo & 3) * 8)) & (ES == 2 ? 0xffffu : 0xffu);
 }
 
-template <typename T>
+// Source voxel (sx, sy) of the pre-rotation view for voxel (u, v) of the
+// rotated view; false: outside (the constant).  Contraction is switched off
+// for this code: the device compiler would otherwise fuse u * c + v * s into
+// an FMA, whose single rounding differs from scipy's at exact .5 ties.  (The
+// operators are written out: the __dmul_rn / __dadd_rn of the device headers
+// are plain * and + that inline with their own contraction flags.)  The inside
+// test is written with positive comparisons, so a NaN coordinate is outside,
+// and the conversion to int comes after it (0 <= floor(c + .5) <= n - 1 then).
+__device__ __forceinline__ bool aug_rot_source(const hcu_ingest_job &J, int u, int v, int &sx, int &sy) {
+#pragma clang fp contract(off)
+  const double du = (double)u, dv = (double)v;
+  const double xa = du * J.rot_m[0], xb = dv * J.rot_m[1];
+  const double ya = du * J.rot_m[2], yb = dv * J.rot_m[3];
+  const double xs = xa + xb, ys = ya + yb;
+  const double cx = xs + J.rot_off[0], cy = ys + J.rot_off[1];
+  const bool inside = cx >= 0.0 && cx <= (double)(J.rot_nx - 1) && cy >= 0.0 && cy <= (double)(J.rot_ny - 1);
+  if (!inside) return false;
+  sx = (int)floor(cx + 0.5);
+  sy = (int)floor(cy + 0.5);
+  return true;
+}
+
+template <typename T, bool ROT>
 __device__ __forceinline__ void aug_job_tile(const hcu_ingest_job &J, const AugTiling &jt, int job, int t,
                                              uint16_t *tile) {
   constexpr int ES = (int)sizeof(T);
@@ -132,16 +166,30 @@ __device__ __forceinline__ void aug_job_tile(const hcu_ingest_job &J, const AugT
 
   // load: x fastest (the source's contiguous direction), program, LDS [c][x][y][z]
   const int nvox = kAugTX * ty * tz;
+  // ROT: the source of this thread's tile column.  xi never changes between a
+  // thread's iterations and yi only when ty does not divide 8, so the
+  // coordinates are computed once per (x, y) and reused for the z rows.
+  int col_y = -1, rx = 0, ry = 0;
+  bool inside = true;
   for (int i = tid; i < nvox; i += 256) {
     const int xi = i & (kAugTX - 1), r = i >> 5, yi = r % ty, zi = r / ty;
     if (xi >= nx || yi >= ny || zi >= nz) continue;
-    const int sx = xmap ? xmap[xb + xi] : J.x0 + xb + xi;
-    const int sy = ymap ? ymap[yb + yi] : J.y0 + yb + yi;
+    int vx = xb + xi, vy = yb + yi;   // voxel of the (pre-rotation) view
+    if constexpr (ROT) {
+      if (yi != col_y) {
+        inside = aug_rot_source(J, J.rot_px + vx, J.rot_py + vy, rx, ry);
+        col_y = yi;
+      }
+      vx = inside ? rx : 0;
+      vy = inside ? ry : 0;
+    }
+    const int sx = xmap ? xmap[vx] : J.x0 + vx;
+    const int sy = ymap ? ymap[vy] : J.y0 + vy;
     const int sz = J.z0 + zb + zi;
     const uint32_t voff = ((uint32_t)sz * Y + sy) * X + sx;                 // < 2^31 / (C * ES): validated
     const uint32_t ovox = ((uint32_t)(xb + xi) * oy + yb + yi) * oz + zb + zi;
     uint32_t w[4] = {0, 0, 0, 0};
-    if (vec) {
+    if (vec && (!ROT || inside)) {
       const char *p = (const char *)src + (size_t)voff * vb;
       if (vb == 16) {
         const uint4 q = *(const uint4 *)p;
@@ -161,9 +209,16 @@ __device__ __forceinline__ void aug_job_tile(const hcu_ingest_job &J, const AugT
     for (int c = 0; c < nc; c += 2) {
       const bool two = c + 1 < nc;
       const int k0 = J.chan[c], k1 = two ? J.chan[c + 1] : k0;
-      double v0 = (double)(vec ? aug_elem<ES>(w, k0) : (uint32_t)src[(size_t)voff * C + k0]) * scale;   // exact
-      double v1 = (double)(vec ? aug_elem<ES>(w, k1) : (uint32_t)src[(size_t)voff * C + k1]) * scale;
-      for (int s = 0; s < nsteps; ++s) {
+      double v0, v1;
+      int s0 = 0;
+      if (!ROT || inside) {
+        v0 = (double)(vec ? aug_elem<ES>(w, k0) : (uint32_t)src[(size_t)voff * C + k0]) * scale;   // exact
+        v1 = (double)(vec ? aug_elem<ES>(w, k1) : (uint32_t)src[(size_t)voff * C + k1]) * scale;
+      } else {   // outside the rotated source: 0.0 as of step fill_after
+        v0 = v1 = 0.0;
+        s0 = J.fill_after;
+      }
+      for (int s = s0; s < nsteps; ++s) {
         const hcu_aug_step &S = J.steps[s];
         const int c1 = two ? c + 1 : c;
         if (S.kind == HCU_AUG_SPEKLE) {
@@ -223,10 +278,16 @@ __global__ void __launch_bounds__(256) ingest_jobs_kernel(const hcu_ingest_job *
   }
   if (t >= jt.tiles) return;   // (the grid is the sum of the jobs' tiles)
   const hcu_ingest_job &J = jobs[j];
-  if (J.src_dtype == HCU_U16)
-    aug_job_tile<uint16_t>(J, jt, j, t, tile);
-  else
-    aug_job_tile<uint8_t>(J, jt, j, t, tile);
+  if (J.rot) {
+    if (J.src_dtype == HCU_U16)
+      aug_job_tile<uint16_t, true>(J, jt, j, t, tile);
+    else
+      aug_job_tile<uint8_t, true>(J, jt, j, t, tile);
+  } else if (J.src_dtype == HCU_U16) {
+    aug_job_tile<uint16_t, false>(J, jt, j, t, tile);
+  } else {
+    aug_job_tile<uint8_t, false>(J, jt, j, t, tile);
+  }
 }
 
 static bool aug_map_ok(const int *m, int n, int limit) {
@@ -256,9 +317,29 @@ static int aug_validate(const hcu_ingest_job &J, int idx) {
   if (J.z0 < 0 || (int64_t)J.z0 + J.oz > J.Z) return fail(HCU_ERR_SHAPE, at + "z window outside the source");
   if ((J.xmap_dev == nullptr) != (J.xmap_host == nullptr) || (J.ymap_dev == nullptr) != (J.ymap_host == nullptr))
     return fail(HCU_ERR_INVALID, at + "an index map needs its device and its host copy");
-  if (J.xmap_host ? !aug_map_ok(J.xmap_host, J.ox, J.X) : (J.x0 < 0 || (int64_t)J.x0 + J.ox > J.X))
+  if (J.rot != 0 && J.rot != 1) return fail(HCU_ERR_INVALID, at + "rot must be 0 or 1");
+  int vx = J.ox, vy = J.oy;   // extents of the view the window / maps describe: the pre-rotation view with rot
+  if (J.rot) {
+    for (int i = 0; i < 4; ++i)
+      if (!(std::fabs(J.rot_m[i]) <= 1.0)) return fail(HCU_ERR_INVALID, at + "rotation matrix entry not in [-1, 1]");
+    if (!std::isfinite(J.rot_off[0]) || !std::isfinite(J.rot_off[1]))
+      return fail(HCU_ERR_INVALID, at + "rotation offset not finite");
+    if (J.rot_nx <= 0 || J.rot_ny <= 0) return fail(HCU_ERR_SHAPE, at + "empty pre-rotation view");
+    if (J.rot_px < 0 || (int64_t)J.rot_px + J.ox > J.rot_nx || J.rot_py < 0 || (int64_t)J.rot_py + J.oy > J.rot_ny)
+      return fail(HCU_ERR_SHAPE, at + "output window outside the rotated view");
+    if (J.fill_after < 0 || J.fill_after > J.n_steps)
+      return fail(HCU_ERR_INVALID, at + "fill_after outside [0, n_steps]");
+    vx = J.rot_nx;
+    vy = J.rot_ny;
+  } else {
+    bool zero = J.rot_nx == 0 && J.rot_ny == 0 && J.rot_px == 0 && J.rot_py == 0 && J.fill_after == 0 &&
+                J.rot_off[0] == 0 && J.rot_off[1] == 0;   // (NaN != 0)
+    for (int i = 0; i < 4; ++i) zero = zero && J.rot_m[i] == 0;
+    if (!zero) return fail(HCU_ERR_INVALID, at + "rotation fields set without rot");
+  }
+  if (J.xmap_host ? !aug_map_ok(J.xmap_host, vx, J.X) : (J.x0 < 0 || (int64_t)J.x0 + vx > J.X))
     return fail(HCU_ERR_SHAPE, at + "x window or map entry outside the source");
-  if (J.ymap_host ? !aug_map_ok(J.ymap_host, J.oy, J.Y) : (J.y0 < 0 || (int64_t)J.y0 + J.oy > J.Y))
+  if (J.ymap_host ? !aug_map_ok(J.ymap_host, vy, J.Y) : (J.y0 < 0 || (int64_t)J.y0 + vy > J.Y))
     return fail(HCU_ERR_SHAPE, at + "y window or map entry outside the source");
   if (((uintptr_t)J.xmap_dev % 4) || ((uintptr_t)J.ymap_dev % 4)) return fail(HCU_ERR_INVALID, at + "misaligned map");
   for (int c = 0; c < J.n_chan; ++c)
@@ -283,6 +364,7 @@ extern "C" int hcu_ingest_jobs(const hcu_ingest_job *jobs_host, const hcu_ingest
     const hcu_ingest_job &J = jobs_host[j];
     if (const int rc = aug_validate(J, j)) return rc;
     tiles += aug_tiling(J.n_chan, J.ox, J.oy, J.oz).tiles;
+    // (a rotated job gathers at most one source voxel per output voxel: its reads count as its outputs)
     bytes += (double)J.ox * J.oy * J.oz * (J.C * (J.src_dtype == HCU_U16 ? 2 : 1) + J.n_chan * 2);
   }
   if (tiles > 0x7fffffff) return fail(HCU_ERR_UNSUPPORTED, "ingest_jobs: too many tiles");

@@ -88,7 +88,7 @@ class _Raw:
 
 
 _LAZY = (t.to_float, t.reshape, t.normalize, t.to_tensor, t.random_crop, t.nul_crop, t.random_intensity,
-         t.drop_channel, t.clean_image, t.remove_channel, t.random_gamma, t.spekle)
+         t.drop_channel, t.clean_image, t.remove_channel, t.random_gamma, t.spekle, t.random_rotate)
 
 
 def _arrays_for(transform, items):

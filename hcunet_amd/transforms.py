@@ -1,15 +1,16 @@
 """Drop-in hcat.transforms for the input path: to_float,
-reshape, normalize and to_tensor, and the reference's crop and intensity
-augmentations -- random_crop, nul_crop, random_intensity, drop_channel,
-clean_image, remove_channel, random_gamma, spekle -- with the reference's
-names, constructor signatures, call convention (joint lists through
+reshape, normalize and to_tensor, and the reference's crop, rotation and
+intensity augmentations -- random_crop, nul_crop, random_rotate,
+random_intensity, drop_channel, clean_image, remove_channel, random_gamma,
+spekle -- with the reference's names, constructor signatures, call convention (joint lists through
 `joint_transform`, which also draws the reference's per-call numpy seed,
 hcat/transforms.py:15-91), exception types and draws from numpy's global RNG
 in the reference's order.
 
 The MI355X path is lazy: a transform only records on the `PendingVolume` what
 it would do to the raw stack -- a window or keep list per axis, a channel
-selection, and an ordered program of at most 8 per-voxel steps -- and
+selection, at most one nearest-neighbour rotation in the (x, y) plane, and an
+ordered program of at most 8 per-voxel steps -- and
 to_tensor runs the whole chain of every volume it is given as ONE device pass
 (csrc/augment.hip, `hcu_ingest_jobs`): the window of the raw uint16 / uint8
 stack is read from HBM, scaled, transposed [Z,Y,X,C] -> [C,X,Y,Z], run through
@@ -28,8 +29,17 @@ given numpy's RNG, with two documented exceptions:
   gain 1); scikit-image itself was not available to pin against, and the
   device's float64 pow may differ from the host's in the last bit.
 
+`random_rotate` is scipy.ndimage.rotate(order=0, mode='constant',
+reshape=False) restated (`rotate_nearest`): float64 source coordinates with
+every product and sum rounded on its own, scipy.special's cosdg / sindg (the
+360 integer angles from the committed table cosdg_sindg.txt), zeros outside.
+The device gathers with the same arithmetic, so it is bit-identical too.  The
+package does not import scipy.ndimage; only a non-integer angle imports
+scipy.special.
+
 Whatever the device program cannot hold (a float64 or 2-D image, a ninth step,
-random_gamma after normalize, ...) runs on the host exactly as the reference's
+random_gamma after normalize, a rotation before reshape or to_float, a second
+rotation, nul_crop after a rotation, ...) runs on the host exactly as the reference's
 numpy code would: `PendingVolume.to_ndarray()` restates every recorded step
 eagerly, taking the window from the raw stack before converting.  Steps are
 never reordered.
@@ -37,13 +47,15 @@ never reordered.
 Reference: to_float hcat/transforms.py:94-116, to_tensor :118-137,
 reshape :139-157, spekle :159-183, random_gamma :186-197, normalize :257-283,
 drop_channel :285-298, random_intensity :301-334, random_crop :337-396,
+random_affine :200-227 (its constructor raises), random_rotate :230-254,
 nul_crop :460-489, remove_channel :590-613, clean_image :616-631.
-elastic_deform, random_rotate, random_affine and the Faster-RCNN box
-transforms of that file are not provided.
+elastic_deform and the Faster-RCNN box transforms of that file are not
+provided.
 """
 import copy
 import ctypes
 import functools
+import os
 
 import numpy as np
 import torch
@@ -68,10 +80,77 @@ class Step:
         self.kind, self.a, self.b, self.key = kind, a, b, key
 
 
+class Rotation:
+    """A recorded random_rotate: cosine and sine of the angle, the extents
+    (nx, ny) of the view it rotated, the number of per-voxel steps recorded
+    before it, and the window (px, py, ox, oy) that later crops left of the
+    rotated view."""
+
+    def __init__(self, c, s, nx, ny, after):
+        self.c, self.s, self.nx, self.ny, self.after = c, s, nx, ny, after
+        self.px, self.py, self.ox, self.oy = 0, 0, nx, ny
+
+
+def rotation_terms(c, s, nx, ny):
+    """scipy.ndimage.rotate's matrix [[c, s], [-s, c]] and offset
+    centre - matrix @ centre (float64, numpy's matmul as scipy calls it) for an
+    (nx, ny) plane rotated about its centre without reshaping."""
+    m = np.array([[c, s], [-s, c]], dtype=np.float64)
+    centre = (np.array([nx, ny]) - 1) / 2
+    return m, centre - m @ centre
+
+
+def rotate_nearest(a, c, s):
+    """scipy.ndimage.rotate(a, axes=(0, 1), reshape=False, order=0,
+    mode='constant', prefilter=False) of the float array a for the angle whose
+    cosdg / sindg are c / s: output (u, v) takes input (floor(cx + .5),
+    floor(cy + .5)), cx = (u c + v s) + off_x, cy = (u (-s) + v c) + off_y with
+    each product and sum rounded on its own, when 0 <= cx <= nx - 1 and
+    0 <= cy <= ny - 1, else 0."""
+    nx, ny = a.shape[:2]
+    m, off = rotation_terms(c, s, nx, ny)
+    u = np.arange(nx, dtype=np.float64)[:, None]
+    v = np.arange(ny, dtype=np.float64)[None, :]
+    cx = (u * m[0, 0] + v * m[0, 1]) + off[0]
+    cy = (u * m[1, 0] + v * m[1, 1]) + off[1]
+    inside = (cx >= 0) & (cx <= nx - 1) & (cy >= 0) & (cy <= ny - 1)
+    ix = np.where(inside, np.floor(cx + 0.5), 0).astype(np.intp)
+    iy = np.where(inside, np.floor(cy + 0.5), 0).astype(np.intp)
+    out = a[ix, iy]
+    out[~inside] = 0
+    return out
+
+
+_COS_SIN = None
+
+
+def cos_sin(angle):
+    """(scipy.special.cosdg(angle), sindg(angle)) as float64: the integer
+    angles 0..359 from the committed table (cosdg_sindg.txt, written by
+    make_cosdg_sindg.py; numpy's cos(deg2rad()) differs in the last bit for
+    most of them), any other angle from scipy.special itself."""
+    global _COS_SIN
+    if float(angle).is_integer() and 0 <= angle < 360:
+        if _COS_SIN is None:
+            with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'cosdg_sindg.txt')) as f:
+                rows = [ln.split() for ln in f if ln.strip() and not ln.startswith('#')]
+            _COS_SIN = [(float.fromhex(r[1]), float.fromhex(r[2])) for r in rows]
+        return _COS_SIN[int(angle)]
+    try:
+        from scipy import special
+    except ImportError as e:
+        raise ImportError('random_rotate needs scipy (scipy.special.cosdg / sindg) for an angle that is not one '
+                          f'of the integers 0..359: {angle}') from e
+    return float(special.cosdg(angle)), float(special.sindg(angle))
+
+
 class PendingVolume:
     """A raw [Z,Y,X,C] (or [Y,X,C]) stack plus the recorded steps, materialised
     by to_tensor on the device: to_float / reshape flags, per raw axis a window
-    (start, n) or an int32 keep list, a channel selection and the program."""
+    (start, n) or an int32 keep list, a channel selection, at most one
+    `Rotation` of the (x, y) plane and the program.  With a rotation the
+    windows / keep lists of x and y describe the view BEFORE it; crops recorded
+    after it move the window (px, py, ox, oy) inside the rotated view."""
 
     def __init__(self, raw, np_dtype=None, source=None):
         self.raw = raw
@@ -84,6 +163,7 @@ class PendingVolume:
         self.sel = [None] * (raw.ndim - 1)   # per raw spatial axis: None (all), (start, n) or int32 array
         self.chan = None                     # source channel of each current channel, or None (all)
         self.steps = []
+        self.rot = None                      # a Rotation, or None
 
     @property
     def ndim(self):  # joint_transform compares ndim across the list (:67-72)
@@ -103,6 +183,8 @@ class PendingVolume:
         s = self._raw_shape()
         if self.reshaped:
             s = (s[-2],) + s[1:-2] + (s[0], s[-1])
+        if self.rot is not None:   # (recorded only on a reshaped [Z,Y,X,C] stack)
+            s = (self.rot.ox, self.rot.oy) + s[2:]
         return s
 
     def uncropped(self):
@@ -118,7 +200,16 @@ class PendingVolume:
 
     def take(self, axis, start=None, n=None, keep=None):
         """Record a window [start, start + n) or the keep list `keep` (indices
-        into the current view) along axis `axis` of the current view."""
+        into the current view) along axis `axis` of the current view.  After a
+        rotation a window along x or y moves inside the rotated view."""
+        if self.rot is not None and axis in (0, 1):
+            if keep is not None:
+                raise NotImplementedError('a keep list after a rotation (nul_crop takes the host path)')
+            if axis == 0:
+                self.rot.px, self.rot.ox = self.rot.px + int(start), int(n)
+            else:
+                self.rot.py, self.rot.oy = self.rot.py + int(start), int(n)
+            return
         r = self._raw_axis(axis)
         old = self.sel[r]
         if keep is not None:
@@ -184,7 +275,11 @@ class PendingVolume:
         code), for transforms that need a real array (the reference's random
         augmentations check isinstance(image, np.ndarray)).  The window is taken
         from the raw stack before converting.  A recorded device spekle step is
-        restated with numpy normals from a generator seeded with its key."""
+        restated with numpy normals from a generator seeded with its key.
+        A recorded rotation (`self.rot`: c, s, nx, ny, after, px, py, ox, oy) is
+        restated by `rotate_nearest` on the (nx, ny) view after the first
+        `after` steps, cut to its window [px, px + ox) x [py, py + oy), and
+        followed by the remaining steps."""
         a = self.windowed_raw()
         if self.to_float and a.dtype == np.uint16:
             a = a.astype(np.float64) / 2 ** 16
@@ -196,8 +291,15 @@ class PendingVolume:
             a = a.swapaxes(a.ndim - 2, 0)
         if self.steps:
             a = np.ascontiguousarray(a)
-        for st in self.steps:
+        R = self.rot
+        for st in self.steps[:len(self.steps) if R is None else R.after]:
             a = _eager_step(a, st)
+        if R is not None:
+            a = rotate_nearest(a, R.c, R.s)[R.px:R.px + R.ox, R.py:R.py + R.oy]
+            if len(self.steps) > R.after:
+                a = np.ascontiguousarray(a)
+            for st in self.steps[R.after:]:
+                a = _eager_step(a, st)
         return a
 
     def _dtype_code(self):
@@ -305,6 +407,8 @@ class reshape:
         if not isinstance(image, (np.ndarray, PendingVolume, torch.Tensor)):
             raise TypeError(f'Expected input type of np.ndarray but got {type(image)}')
         v = _wrap(image)
+        if v.rot is not None:   # the rotation plane would no longer be raw (X, Y): the rest on the host
+            v = PendingVolume(v.to_ndarray())
         if v.reshaped:   # a second swap undoes the first
             v.reshaped = False
         else:
@@ -437,7 +541,8 @@ class nul_crop:
     empty, from every volume of the list (:460-489).  Recorded as keep lists on
     the raw stacks; the lists come from the raw integer mask on the host and are
     cached per stack while the volume is uncropped.  Float masks take the host
-    path."""
+    path, and so does a list with a recorded rotation (the keep lists would
+    need the rotated mask)."""
 
     def __init__(self, rate=1):
         self.rate = rate
@@ -448,7 +553,7 @@ class nul_crop:
         if not np.random.random() < self.rate:
             return image_list
         mask = image_list[1]
-        lazy = (all(isinstance(v, PendingVolume) and v.raw.ndim == 4 for v in image_list)
+        lazy = (all(isinstance(v, PendingVolume) and v.raw.ndim == 4 and v.rot is None for v in image_list)
                 and mask._dtype_code() in _INT_CODES and mask.shape[-1] == 1 and not mask.steps
                 and (not isinstance(mask.raw, torch.Tensor) or mask.raw.device.type == 'cpu'))
         if lazy:
@@ -474,6 +579,45 @@ class nul_crop:
         m = arrays[1]
         ud = m.sum(axis=0).sum(axis=1).flatten() > 1
         return [PendingVolume(a[:, ud, :, :]) for a in arrays]
+
+
+class random_rotate:
+    """scipy.ndimage.rotate of the (x, y) plane by `angle` degrees, nearest
+    neighbour, same extents, zeros outside (:230-254); the same angle for every
+    volume of a joint list.  `if not self.angle` (None and 0 alike) re-seeds
+    numpy's global RNG with the joint seed and draws randint(0, 360); a given
+    angle draws nothing.  Recorded for the device on an integer [Z,Y,X,C] stack
+    with to_float and reshape applied and no rotation yet: the kernel gathers
+    with `rotate_nearest`'s arithmetic.  Anything else is rotated on the host."""
+
+    def __init__(self, angle=None):
+        self.angle = angle
+
+    @joint_transform
+    def __call__(self, image, seed):
+        if not isinstance(image, (np.ndarray, PendingVolume)):
+            raise TypeError(f'Expected list of images as input, but got {type(image)}')
+        if not self.angle:
+            np.random.seed(seed)
+            theta = np.random.randint(0, 360, 1)[0]
+        else:
+            theta = self.angle
+        c, s = cos_sin(theta)
+        v = _wrap(image)
+        if (v.raw.ndim == 4 and v._dtype_code() in _INT_CODES and v.to_float and v.reshaped and v.rot is None
+                and v.raw.shape[-1] <= _lib.INGEST_MAX_C):
+            nx, ny = v.shape[:2]
+            v.rot = Rotation(c, s, nx, ny, len(v.steps))
+            return v
+        return PendingVolume(rotate_nearest(_host(v).astype(np.float64), c, s))
+
+
+class random_affine:
+    """The reference's constructor fails before anything else (:200-203): it
+    raises the NotImplemented constant, which is not callable, so a TypeError."""
+
+    def __init__(self):
+        raise NotImplemented('hcat.transforms.random_affine is unusable in the reference and not provided')
 
 
 class random_intensity:
@@ -645,7 +789,8 @@ def _ingest_volume(v, device):
     code = v._dtype_code()
     if code is None:
         raise TypeError('Expected image datatype of uint8 or uint16 ')
-    if not v.uncropped() or v.chan is not None or any(st.kind != NORMALIZE for st in v.steps) or len(v.steps) > 1:
+    if (not v.uncropped() or v.chan is not None or v.rot is not None or len(v.steps) > 1
+            or any(st.kind != NORMALIZE for st in v.steps)):
         v = PendingVolume(v.to_ndarray())   # the recorded steps on the host; the device pass only rounds
         code = v._dtype_code()
         if code is None:
@@ -677,7 +822,8 @@ def _ingest_volume(v, device):
 
 def _is_job(v):
     """Volumes hcu_ingest_jobs takes: integer [Z,Y,X,C] stacks with reshape
-    applied, a plain z window and at most 16 channels."""
+    applied, a plain z window and at most 16 channels (a recorded rotation
+    implies all of these)."""
     return (v.raw.ndim == 4 and v._dtype_code() in _INT_CODES and v.reshaped
             and not isinstance(v.sel[0], np.ndarray) and v.raw.shape[-1] <= _lib.INGEST_MAX_C)
 
@@ -688,6 +834,14 @@ def _fill_job(job, v, raw, dst, maps, host_base, dev_base):
     job.src, job.dst = raw.data_ptr(), dst.data_ptr()
     job.src_dtype, job.Z, job.Y, job.X, job.C = code, Z, Y, X, C
     oz, oy, ox, nc = v._raw_shape()
+    R = v.rot
+    if R is not None:   # the window / maps below describe the pre-rotation view of ox by oy voxels
+        m, off = rotation_terms(R.c, R.s, ox, oy)
+        job.rot, job.fill_after = 1, R.after
+        job.rot_m[:] = [float(x) for x in m.reshape(-1)]
+        job.rot_off[:] = [float(x) for x in off]
+        job.rot_nx, job.rot_ny, job.rot_px, job.rot_py = ox, oy, R.px, R.py
+        ox, oy = R.ox, R.oy
     job.ox, job.oy, job.oz = ox, oy, oz
     job.z0 = 0 if v.sel[0] is None else v.sel[0][0]
     for name, w in (('y', v.sel[1]), ('x', v.sel[2])):
@@ -748,7 +902,7 @@ def materialise_many(vols, dsts=None, device=None):
             for k, i in enumerate(jobs):
                 v = vols[i]
                 raws.append(_device_raw(v, device))
-                oz, oy, ox, nc = v._raw_shape()
+                ox, oy, oz, nc = v.shape
                 out = _lib.empty((1, nc, ox, oy, oz), torch.float16, device) if dsts is None else dsts[i]
                 _fill_job(table[k], v, raws[-1], out, maps, host.data_ptr(), dev.data_ptr())
                 outs[i] = out

@@ -413,6 +413,21 @@ int hcu_ingest_volume(const void *src, int src_dtype, int B, int Z, int Y, int X
 /*                        pair; Box-Muller in float64, cosine branch for the   */
 /*                        even channel, sine for the odd): the distribution of */
 /*                        spekle (:159-183), not numpy's stream;               */
+/*   rotation (rot = 1) random_rotate (:230-254): scipy.ndimage.rotate in the  */
+/*            (x, y) plane, order 0, zeros outside.  The window above then     */
+/*            describes the PRE-rotation view of rot_nx by rot_ny voxels (maps */
+/*            of rot_nx / rot_ny entries) and output (i, j, k) is voxel        */
+/*            (u, v) = (rot_px + i, rot_py + j) of the rotated view, whose     */
+/*            source is, in float64 with every product and sum rounded on its  */
+/*            own (no fused multiply-add),                                     */
+/*              cx = (u * rot_m[0] + v * rot_m[1]) + rot_off[0]                */
+/*              cy = (u * rot_m[2] + v * rot_m[3]) + rot_off[1]                */
+/*            view voxel (floor(cx + 0.5), floor(cy + 0.5)) when               */
+/*            0 <= cx <= rot_nx - 1 and 0 <= cy <= rot_ny - 1, and otherwise   */
+/*            the constant 0.0 AS OF STEP fill_after: steps [0, fill_after)    */
+/*            act on the gathered source value only, an outside voxel starts   */
+/*            from 0.0 and runs steps [fill_after, n_steps).  Not a step kind: */
+/*            a rotation takes no program slot.                                */
 /*   rounding float64 -> float32 -> fp16, each to nearest even (torch's).     */
 /* jobs_host is the table in host memory, jobs_dev the caller's copy of it in */
 /* device memory (copied on `stream` before the call); xmap_host / ymap_host  */
@@ -422,7 +437,11 @@ int hcu_ingest_volume(const void *src, int src_dtype, int B, int Z, int Y, int X
 /* HCU_INGEST_MAX_C channels, more than HCU_AUG_MAX_STEPS steps, or a source  */
 /* or destination of 2^31 bytes / elements or more, HCU_ERR_UNSUPPORTED;      */
 /* other dtypes, step kinds, channel indices and null pointers                */
-/* HCU_ERR_INVALID.                                                           */
+/* HCU_ERR_INVALID.  With rot: rot other than 0 / 1, a matrix or offset entry */
+/* that is not finite or a matrix entry beyond 1 in magnitude, fill_after      */
+/* outside [0, n_steps] is HCU_ERR_INVALID; rot_nx / rot_ny <= 0 or an output  */
+/* window (rot_px, ox) / (rot_py, oy) outside the rotated view HCU_ERR_SHAPE.  */
+/* Without rot every rot_* field and fill_after must be 0 (HCU_ERR_INVALID).   */
 /* ------------------------------------------------------------------------ */
 #define HCU_INGEST_MAX_C 16
 #define HCU_AUG_MAX_STEPS 8
@@ -436,7 +455,7 @@ typedef struct hcu_aug_step {
 typedef struct hcu_ingest_job {
   const void *src;                   /* device, [Z][Y][X][C] of src_dtype */
   void *dst;                         /* device, fp16 [n_chan][ox][oy][oz] */
-  const int *xmap_dev, *ymap_dev;    /* device int32 [ox] / [oy], or null: origin */
+  const int *xmap_dev, *ymap_dev;    /* device int32 [ox] / [oy] ([rot_nx] / [rot_ny] with rot), or null: origin */
   const int *xmap_host, *ymap_host;  /* the same entries in host memory */
   int src_dtype, Z, Y, X, C;
   int ox, oy, oz;                    /* output extent along the source's x, y, z */
@@ -445,6 +464,12 @@ typedef struct hcu_ingest_job {
   int n_steps;
   double scale;                      /* to_float: 2^-16, 2^-8, or 1 */
   hcu_aug_step steps[HCU_AUG_MAX_STEPS];
+  int rot;                           /* 1: rotated gather in the (x, y) plane; 0: every field below is 0 */
+  double rot_m[4];                   /* c, s, -s, c (scipy.special.cosdg / sindg of the angle) */
+  double rot_off[2];                 /* centre - rot_m @ centre, centre = ((rot_nx - 1) / 2, (rot_ny - 1) / 2) */
+  int rot_nx, rot_ny;                /* extents of the pre-rotation view (and of the maps) */
+  int rot_px, rot_py;                /* origin of the output window in the rotated view */
+  int fill_after;                    /* 0..n_steps: steps that ran before the rotation */
 } hcu_ingest_job;
 int hcu_ingest_jobs(const hcu_ingest_job *jobs_host, const hcu_ingest_job *jobs_dev, int n_jobs,
                     hcu_stream_t stream);

@@ -17,6 +17,12 @@ plus random_gamma and spekle, cropped to 256x256x16:
                    This is the only way to run the recipe on a tree whose
                    hcat.transforms lacks the classes, so it also runs there.
 
+  --rotate         appends random_rotate() to the joint chain, after random_crop
+                   (the reference's geometric step, hcat/transforms.py:230-254):
+                   ht.random_rotate() in device mode, one more job field of the
+                   same launch; in fallback mode a caller's own class that
+                   calls scipy.ndimage.rotate as the reference does.
+
 Batches are timed with device events around the whole loop after a warm-up
 (the consumer only waits for each batch, so this is the input path alone).
 Prints one JSON line.  `--merge RESULT.json --stats-csv KERNEL_STATS.csv` runs
@@ -66,6 +72,17 @@ class np_random_crop:
         return [v[o[0]:o[0] + d[0], o[1]:o[1] + d[1], o[2]:o[2] + d[2]] for v in vols]
 
 
+class np_random_rotate:
+    """The reference's random_rotate on a list, with scipy as it calls it."""
+
+    def __call__(self, vols):
+        from scipy import ndimage
+        np.random.seed(np.random.randint(0, 1e8, 1))
+        theta = np.random.randint(0, 360, 1)[0]
+        return [ndimage.rotate(v.astype(float), axes=(0, 1), angle=theta, reshape=False, order=0, mode='constant',
+                               prefilter=False) for v in vols]
+
+
 class np_augment:
     """random_gamma, random_intensity, drop_channel, spekle, clean_image on a float image."""
 
@@ -100,7 +117,7 @@ def make_stacks(seed, n, X, Y, Z):
     return files
 
 
-def build(mode, files, tmp):
+def build(mode, files, tmp, rotate=False):
     for n in files:
         open(os.path.join(tmp, n), 'wb').close()
     if mode == 'device':
@@ -110,6 +127,8 @@ def build(mode, files, tmp):
     else:
         joint = [ht.to_float(), ht.reshape(), np_nul_crop(), np_random_crop(CROP)]
         image = [np_augment(), ht.normalize([.5] * 4, [.5] * 4)]
+    if rotate:
+        joint.append(ht.random_rotate() if mode == 'device' else np_random_rotate())
     return hdl.Stack(tmp, image_transforms=image, joint_transforms=joint,
                      reader=lambda p: files[os.path.basename(p)])
 
@@ -141,6 +160,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--size', type=int, nargs=3, default=[1024, 1024, 32], metavar=('X', 'Y', 'Z'))
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--rotate', action='store_true')
     ap.add_argument('--stats-csv', default=None)
     ap.add_argument('--merge', default=None)
     args = ap.parse_args()
@@ -156,7 +176,7 @@ def main():
         raise SystemExit('input_bench: no ROCm device (a time measured without one means nothing)')
     files = make_stacks(args.seed, 2, *args.size)
     with tempfile.TemporaryDirectory() as tmp:
-        data = build(args.mode, files, tmp)
+        data = build(args.mode, files, tmp, args.rotate)
         np.random.seed(args.seed)
         for out in batches(args.mode, data, args.batch, args.warmup):
             pass
@@ -172,8 +192,10 @@ def main():
     B = args.batch
     vox = CROP[0] * CROP[1] * CROP[2]
     # per item: image 4 x uint16 read + 4 x fp16 written, mask uint8 + fp16, pwl uint16 + fp16
+    # (with --rotate a voxel whose source lies outside reads nothing: an upper bound then)
     nbytes = B * vox * ((8 + 8) + (1 + 2) + (2 + 2))
-    res = dict(tool='input_bench', mode=args.mode, batch=B, batches=args.batches, warmup=args.warmup,
+    res = dict(tool='input_bench', mode=args.mode, rotate=args.rotate, batch=B, batches=args.batches,
+               warmup=args.warmup,
                stack=args.size, crop=CROP, out_shape=list(out[0].shape),
                ms_per_batch=e0.elapsed_time(e1) / args.batches, host_ms_per_batch=host_ms,
                kernel_bytes_per_batch=nbytes)
