@@ -49,16 +49,7 @@ static long bconv_lds(const GConvArgs &a, int CV, int NT) {
           3L * a.ICs) * 4 + (long)sizeof(GConvArgs);   // + the static copy of the arguments
 }
 
-int bconv_stat_rows(const GConvArgs &a) {
-  if (a.ksplit > 1) {
-    const int64_t nvox = (int64_t)a.B * a.SX * a.SY * a.SZ;
-    const int vpb = bconv_reduce_vpb(a);
-    return (int)((nvox + vpb - 1) / vpb);
-  }
-  return a.gridx;   // one row per block
-}
-
-static void bconv_finish(GConvArgs &a, int ntz, int VEC, int fpf, long lds_cap);
+static void bconv_finish(GConvArgs &a, int ntz, int VEC, int fpf);
 static void bconv_halo_layout(GConvArgs &a, int CV, long lds_cap);
 
 // ---- measured planning: times a candidate on scratch buffers of its shapes
@@ -159,9 +150,9 @@ static double bconv_time(const GConvArgs &c0) {
   const int T = c.KX * c.KY * c.KZ;
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t b_in = al((size_t)c.B * c.IX * c.IY * c.IZ * c.ICs * es);
-  const size_t b_w = al((size_t)wpack_count(wpack_of(c), T, c.ICs, c.CoutW) * es);
+  const size_t b_w = al((size_t)wpack_count(wpack_make(es == 4 ? 1 : 3, c), T, c.ICs, c.CoutW) * es);
   const size_t b_out = al((size_t)c.B * c.SX * c.SY * c.SZ * c.OCs * es);
-  const size_t b_st = al((size_t)bconv_stat_rows(c) * c.CoutW * 4 * sizeof(float));
+  const size_t b_st = al((size_t)ksplit_stat_rows(c, 16 / (int)es) * c.CoutW * 4 * sizeof(float));
   const size_t b_part = c.ksplit > 1 ? al((size_t)c.ksplit * c.slice_floats * sizeof(float)) : 0;
   const size_t b_vec = al((size_t)std::max(std::max(c.ICs, c.OCs), c.Cout) * sizeof(float));
   const size_t need = b_in + b_w + 2 * b_out + b_st + b_part + 6 * b_vec;
@@ -222,7 +213,6 @@ static double bconv_time(const GConvArgs &c0) {
 }
 
 int plan_bconv(GConvArgs &a, int target_blocks) {
-  a.use_bconv = 0;
   if (a.bes == 0) a.bes = 2;
   if (a.bes != 2 && a.bes != 4) return fail(4, "bconv: element size must be 2 (bf16) or 4 (fp32)");
   const int VEC = 16 / a.bes;
@@ -338,7 +328,7 @@ int plan_bconv(GConvArgs &a, int target_blocks) {
   if (cands.empty()) return fail(4, "bconv: no tile fits in LDS");
   std::stable_sort(cands.begin(), cands.end(),
                    [](const Cand &x, const Cand &y) { return x.cost < y.cost; });
-  for (Cand &cd : cands) bconv_finish(cd.c, ntz, VEC, fpf, lds_cap);
+  for (Cand &cd : cands) bconv_finish(cd.c, ntz, VEC, fpf);
   // halo image layout: searched only for the candidates that can be chosen
   auto lay = [&](Cand &cd) {
     if (!cd.laid) bconv_halo_layout(cd.c, cd.c.CK / VEC, lds_cap);
@@ -507,7 +497,7 @@ static void bconv_halo_layout(GConvArgs &a, int CV, long lds_cap) {
 }
 
 // Completes a candidate tiling: K split, prefetch depth, persistent grid, divisors.
-static void bconv_finish(GConvArgs &a, int ntz, int VEC, int fpf, long lds_cap) {
+static void bconv_finish(GConvArgs &a, int ntz, int VEC, int fpf) {
   const int NT = a.NSUB * 16;
   const int nN = a.CoutW / NT;
   a.ntx = cdiv(a.OX, a.TX);
@@ -539,11 +529,8 @@ static void bconv_finish(GConvArgs &a, int ntz, int VEC, int fpf, long lds_cap) 
   a.fNT = FastDiv(a.ntx * a.nty * a.ntz);
   a.fNTZ = FastDiv(a.ntz);
   a.fNTY = FastDiv(a.nty);
-  (void)lds_cap;
   a.areg = (int)bconv_areg(a, CV);
-  a.use_bconv = 1;
-  a.use_conv2 = 0;
-  a.use_conv8 = 0;
+  a.kern = KCONV_BCONV;
 }
 
 int launch_bconv_bf16(const GConvArgs &a, hipStream_t s) { BCONV_LAUNCH_BODY(uint16_t, "bf16") }

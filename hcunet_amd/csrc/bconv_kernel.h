@@ -1033,9 +1033,6 @@ __global__ void __launch_bounds__(256) bconv_reduce_kernel(const GConvArgs a, in
   }
 }
 
-// K-split reduce geometry: voxels per reduce block
-inline int bconv_reduce_vpb(const GConvArgs &a) { return 2 * 256 / (a.OCs / (16 / a.bes)); }
-
 int launch_bconv_bf16(const GConvArgs &a, hipStream_t s);
 int launch_bconv_f32(const GConvArgs &a, hipStream_t s);
 
@@ -1091,9 +1088,8 @@ template <> bool bconv_launch_cv<uint16_t, 4>(const GConvArgs &, hipStream_t, co
 
 // Launch of the planned variant (+ the K-split reduce) for element type E.
 #define BCONV_LAUNCH_BODY(E_, TAG_)                                                                  \
-  const dim3 grid(a.gridx, a.CoutW / (a.NSUB * 16), a.ksplit);                                       \
-  if (a.in_fmt && (a.CK != BElem<E_>::VEC || a.NPF == 0 || a.bn_y || a.in_scale || a.ksplit > 1 ||    \
-                   a.nph > 1 || a.in_c < 1 || a.in_c > 4))                                            \
+  const dim3 grid = conv2_grid(a);                                                                   \
+  if (a.in_fmt && !(bconv_ncx_ok(a) && ncx_bound_ok(a)))                                             \
     return fail(4, "bconv: NCXYZ input needs a first-layer forward (one channel group, prefetched)"); \
   if (grid.y > 65535 || grid.z > 65535) return fail(4, "bconv: grid too large");                     \
   if (a.ksplit > 1 && !a.partial) return fail(5, "bconv: K split needs a partial workspace");        \
@@ -1111,7 +1107,7 @@ template <> bool bconv_launch_cv<uint16_t, 4>(const GConvArgs &, hipStream_t, co
   HCU_CHECK_LAUNCH();                                                                                \
   if (a.ksplit > 1) {                                                                                \
     const int64_t nvox = (int64_t)a.B * a.SX * a.SY * a.SZ;                                          \
-    const int vpb = bconv_reduce_vpb(a);                                                             \
+    const int vpb = ksplit_vpb(a, BElem<E_>::VEC);                                                   \
     const int blocks = (int)((nvox + vpb - 1) / vpb);                                                \
     HCU_TIMED(s, "bconv_reduce_kernel<" TAG_ ">", 0.0, (4.0 * a.ksplit + 2.0) * a.slice_floats,      \
               HCU_LAUNCH(bconv_reduce_kernel<E_>, dim3(blocks), dim3(256), 0, s, a, vpb));   \

@@ -729,8 +729,7 @@ static bool alltaps_enabled() {
   return on;
 }
 
-int plan_bwgrad(WGradArgs &a, int target_blocks) {
-  (void)target_blocks;
+int plan_bwgrad(WGradArgs &a) {
   if (a.ACs % 8 || a.GCs % 8) return fail(4, "bwgrad: channel strides must be multiples of 8");
   if (a.PX <= 0 || a.PY <= 0 || a.PZ <= 0) return fail(2, "bwgrad: empty grid");
   // channel chunks: A side up to 32 channels, G side up to 64 (16-col
@@ -748,7 +747,7 @@ int plan_bwgrad(WGradArgs &a, int target_blocks) {
 // for each of its 4 tap chunks and ran at ~3-4 % of bf16 MFMA).  Fails (the
 // caller then takes the split form) for any other shape.
 static int plan_bwgrad_cka(WGradArgs &a, int cka_cap, bool alltaps) {
-  a.use_bw = 0;
+  a.kern = KWG_WGRAD;
   const int T = a.KX * a.KY * a.KZ;
   // padded operands (zero padding of A, or a cropped ConvTranspose3d output
   // as G) are staged as zeros outside their grids
@@ -918,8 +917,7 @@ static int plan_bwgrad_cka(WGradArgs &a, int cka_cap, bool alltaps) {
   long kb = std::max(1L, (long)cus * occ_kb / per);
   kb = std::min(kb, total);
   a.KB = (int)kb;
-  a.use_bw = 1;
-  a.v2 = 0;
+  a.kern = KWG_BWGRAD;
   if (getenv("HCU_CONV2_LOG"))
     fprintf(stderr,
             "bwgrad plan: rows%d A%dx%dx%d ACs%d G%dx%dx%d GCs%d P%dx%dx%d K%dx%dx%d | CKA%d CKG%d "

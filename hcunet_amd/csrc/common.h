@@ -253,13 +253,13 @@ struct GConvArgs {
   int ksplit, cps;                    // K-split count, channel chunks per split
   size_t slice_floats;                // floats of one stored-tensor slice
   float *partial;                     // [ksplit][stored tensor] when ksplit > 1
-  int use_conv2;
+  int kern;                           // ConvKern: the kernel family planned (0: gconv)
   int NPF, gridx;                     // conv2 halo prefetch depth, persistent grid size
   int epi_lds, nc4, areg;             // conv2 epilogue through LDS (float4 stores), float4
                                       // groups, floats of the halo / C-tile LDS region
   FastDiv fNT, fNTZ, fNTY;            // tile index decomposition
   // conv8 (conv8.hip): <= 8 output channels on the 16-block 4x4x1 MFMA
-  int use_conv8, G8, HVP;             // enabled, 32-voxel groups per wave, halo plane stride
+  int rsv0_, G8, HVP;                 // (reserved), 32-voxel groups per wave, halo plane stride
   FastDiv fKZ, fKY;                   // tap index decomposition (conv8 K loop)
   int dbg;                            // ablation bits (HCU_CONV8_DBG; 0 in production)
   int HZr, MZ;                        // conv8: loaded halo z extent, z stride of the M rows
@@ -278,9 +278,11 @@ struct GConvArgs {
   // rows hold (sum dz, sum dz * (y-mean)*invstd) per channel.
   const float *bn_y, *bn_scale, *bn_shift, *bn_mean, *bn_invstd;
   double flops;                       // algorithmic FLOPs (0: derive)
-  // bconv (bconv.hip): the bf16 path.  in / out / bn_y / w point to bf16 data
-  // (channels-last activations, packed weights); partial stays fp32.
-  int use_bconv;
+  // bconv (bconv.hip) with 2-byte elements, the bf16 path: in / out / bn_y / w
+  // point to bf16 data (channels-last activations, packed weights); partial
+  // stays fp32.  (rsv0_ / rsv1_: the kernels take this record by value and
+  // copy it whole into LDS, so its layout is part of the compiled code.)
+  int rsv1_;
   int bes;   // bconv element bytes: 2 (bf16 activations) or 4 (fp32); 0 = 2
   // bconv with ConvTranspose3d phases folded into N: columns per phase (0 =
   // Cout).  Cout not a multiple of the 4 (fp32) / 8 (bf16) columns a lane's
@@ -289,6 +291,63 @@ struct GConvArgs {
   int cph;
 };
 
+// Chooses the tile and kernel variant; returns 0 or an error code.
+int plan_gconv(GConvArgs &a, int target_blocks);
+int launch_gconv(const GConvArgs &a, hipStream_t s);
+int plan_conv2(GConvArgs &a, int target_blocks);
+int launch_conv2(const GConvArgs &a, hipStream_t s);
+int plan_conv8(GConvArgs &a, int target_blocks);
+int launch_conv8(const GConvArgs &a, hipStream_t s);
+int plan_bconv(GConvArgs &a, int target_blocks);
+int launch_bconv(const GConvArgs &a, hipStream_t s);
+void bconv_tuning(bool on);   // measured planning on/off for the plans built by this thread
+// The launch grids: gconv one workgroup per (tile, column block, sample); the
+// persistent kernels gridx workgroups per (column block, K split).
+inline dim3 gconv_grid(const GConvArgs &a) { return dim3(a.ntx * a.nty * a.ntz, a.CoutW / (a.NSUB * 16), a.B); }
+inline dim3 conv2_grid(const GConvArgs &a) { return dim3(a.gridx, a.CoutW / (a.NSUB * 16), a.ksplit); }
+// The K split of conv2 / bconv (vec channels per 16 bytes): voxels per block
+// of the reduce kernel, and the statistics rows of a launch, one per reduce
+// block or, without a split, one per workgroup.
+inline int ksplit_vpb(const GConvArgs &a, int vec) { return 2 * 256 / (a.OCs / vec); }
+inline int ksplit_stat_rows(const GConvArgs &a, int vec) {
+  if (a.ksplit <= 1) return a.gridx;
+  const int64_t nvox = (int64_t)a.B * a.SX * a.SY * a.SZ, vpb = ksplit_vpb(a, vec);
+  return (int)((nvox + vpb - 1) / vpb);
+}
+// Whether the planned instance can stage the network input in the caller's
+// NCXYZ layout (GConvArgs::in_fmt): conv8 with one channel group; bconv with
+// one channel group, a prefetched halo, no K split and no phases; and whether
+// the arguments bound at launch are a first-layer forward's.
+inline bool conv8_ncx_ok(const GConvArgs &a) { return a.ICs == 4; }
+inline bool bconv_ncx_ok(const GConvArgs &a) {
+  return a.CK == (a.bes == 4 ? 4 : 8) && a.NPF > 0 && a.ksplit == 1 && a.nph <= 1;
+}
+inline bool ncx_bound_ok(const GConvArgs &a) { return !a.bn_y && !a.in_scale && a.in_c >= 1 && a.in_c <= 4; }
+
+// ---------------------------------------------------------------------------
+// Kernel families.  A planned GEMM carries one tag (GConvArgs::kern,
+// WGradArgs::kern); what follows from the choice is a field of the family's
+// record, and the ladders that make the choice are plan_conv / plan_wgrad_any
+// (all in families.cpp).  The older families stay as fallbacks and A/B sides.
+enum ConvKern { KCONV_GCONV = 0, KCONV_CONV2, KCONV_CONV8, KCONV_BCONV };
+struct ConvFamily {
+  const char *name;
+  int (*plan)(GConvArgs &, int target_blocks);
+  int (*launch)(const GConvArgs &, hipStream_t);
+  dim3 (*grid)(const GConvArgs &);
+  int (*stat_rows)(const GConvArgs &);   // statistics rows (below) one launch writes
+  bool ksplit;         // may split K over blocks: fp32 partial slices in GConvArgs::partial
+  int wpack, wbytes;   // the weight image: WPack::on and its element bytes
+  bool bnbwd;          // the epilogue can fuse the BatchNorm backward (bn_y)
+  bool folds_phases;   // ConvTranspose3d phases folded into N (nph > 1)
+  bool (*ncx_ok)(const GConvArgs &);     // null: never reads the NCXYZ input
+};
+// bes: the element bytes of a bconv plan (2 / 0: bf16, 4: fp32)
+const ConvFamily &conv_family(int kern, int bes);
+inline const ConvFamily &conv_family(const GConvArgs &a) { return conv_family(a.kern, a.bes); }
+// Plans the convolution `a` on es-byte activations (4 fp32, 2 bf16).
+int plan_conv(GConvArgs &a, int es, int target_blocks);
+inline int launch_conv_any(const GConvArgs &a, hipStream_t s) { return conv_family(a).launch(a, s); }
 // Forward BatchNorm statistics rows (stats, [rows][CoutW] of float4): per
 // (row, channel) {S1, S2, K, n} = sums of (y - K) and (y - K)^2 over the n
 // outputs the row's workgroup produced, K a pivot value taken from those
@@ -296,70 +355,9 @@ struct GConvArgs {
 // identity), so the variance never comes from E[y^2] - E[y]^2 of raw fp32 sums.
 // The fused BatchNorm-backward epilogue (bn_y set) writes plain [rows][CoutW][2]
 // sums (sum dz, sum dz * xhat) into the same buffer.
-// Chooses the tile and kernel variant; returns 0 or an error code.
-int plan_gconv(GConvArgs &a, int target_blocks);
-int launch_gconv(const GConvArgs &a, hipStream_t s);
-int plan_conv2(GConvArgs &a, int target_blocks);
-int launch_conv2(const GConvArgs &a, hipStream_t s);
-size_t conv2_partial_floats(const GConvArgs &a);
-int conv2_stat_rows(const GConvArgs &a);
-int plan_conv8(GConvArgs &a, int target_blocks);
-int launch_conv8(const GConvArgs &a, hipStream_t s);
-// Plans conv2 when it supports the shape, else the generic gconv.
-bool conv2_disabled();   // HCU_NO_CONV2=1 forces the generic kernel (A/B testing)
-inline int plan_conv_any(GConvArgs &a, int target_blocks) {
-  GConvArgs b8 = a;
-  if (plan_conv8(b8, target_blocks) == 0) {
-    a = b8;
-    return 0;
-  }
-  GConvArgs b = a;
-  b.use_conv8 = 0;
-  if (!conv2_disabled() && plan_conv2(b, target_blocks) == 0) {
-    a = b;
-    return 0;
-  }
-  a.use_conv2 = 0;
-  a.use_conv8 = 0;
-  return plan_gconv(a, target_blocks);
-}
-int plan_bconv(GConvArgs &a, int target_blocks);
-// fp32 convolution: the blocked MFMA kernel (bconv, fp32 elements) when it
-// supports the shape, else conv8 / conv2 / the generic gconv.
-// HCU_NO_BCONV_F32=1 restores the older fp32 kernels (A/B testing).
-inline int plan_conv_fp32(GConvArgs &a, int target_blocks) {
-  static const bool off = getenv("HCU_NO_BCONV_F32") != nullptr;
-  // fewer than 16 output columns: conv8's 4x4 MFMA blocks waste no MFMA rows
-  if (!off && a.Cout * std::max(1, a.nph) >= 16) {
-    GConvArgs b = a;
-    b.bes = 4;
-    if (plan_bconv(b, target_blocks) == 0) {
-      a = b;
-      return 0;
-    }
-  }
-  a.cph = 0;   // (bconv only)
-  return plan_conv_any(a, target_blocks);
-}
-int launch_bconv(const GConvArgs &a, hipStream_t s);
-void bconv_tuning(bool on);   // measured planning on/off for the plans built by this thread
-int bconv_stat_rows(const GConvArgs &a);
-inline int launch_conv_any(const GConvArgs &a, hipStream_t s) {
-  if (a.use_bconv) return launch_bconv(a, s);
-  if (a.use_conv8) return launch_conv8(a, s);
-  return a.use_conv2 ? launch_conv2(a, s) : launch_gconv(a, s);
-}
-inline int gconv_rows(const GConvArgs &a) {
-  if (a.use_bconv) return bconv_stat_rows(a);
-  if (a.use_conv8) return a.gridx;
-  return a.use_conv2 ? conv2_stat_rows(a) : a.B * a.ntx * a.nty * a.ntz;
-}
-// Whether the kernel planned in `a` supports the fused BatchNorm-backward epilogue.
-inline bool conv_bnbwd_fusable(const GConvArgs &a) {
-  return a.use_conv8 || a.use_conv2 || a.use_bconv;
-}
+inline int gconv_rows(const GConvArgs &a) { return conv_family(a).stat_rows(a); }
 inline size_t conv_partial_floats(const GConvArgs &a) {
-  return ((a.use_conv2 || a.use_bconv) && !a.use_conv8) ? conv2_partial_floats(a) : 0;
+  return conv_family(a).ksplit && a.ksplit > 1 ? (size_t)a.ksplit * a.slice_floats : 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -382,7 +380,7 @@ struct WGradArgs {
   int gsx, gsy, gsz, gdx, gdy, gdz, gpx, gpy, gpz;
   int taps_rows, bias_row;
   int Mtot, Ntot;
-  // tiling (filled by plan_wgrad)
+  // tiling (filled by plan_wgrad_generic)
   int TX, TY, TZ, ntx, nty, ntz;
   int HAX, HAY, HAZ, PA, HGX, HGY, HGZ, PG;
   int CKA, CKG, mloc, nloc, MS, NS;
@@ -393,15 +391,16 @@ struct WGradArgs {
   FastDiv fHAZ, fHAY, fHGZ, fHGY, fTZ, fTY;
   // wgrad2 (Conv3d, stride-1 operands): z rows padded to multiples of 4 so a
   // lane reads 4 consecutive voxels with one ds_read_b128; one A image per kz.
-  int v2, TZP, HAZP, PA2, PG2, gridx, occ;
+  int kern, TZP, HAZP, PA2, PG2, gridx, occ;   // kern: WGradKern, the kernel family planned (0: wgrad)
   double flops;                       // algorithmic FLOPs (0: derive)
   // bwgrad (bwgrad.hip): the bf16 path (A, G bf16 channels-last); PA2 / PG2
   // are the LDS row strides of the A halo / G images, MSW the row subtiles per
-  // wave, NSB the column subtiles of a block.
-  int use_bw, MSW, NSB, PTV, HAV, HGV;
+  // wave, NSB the column subtiles of a block.  (rsv0_: reserved, the layout
+  // is part of the compiled kernels as GConvArgs' is.)
+  int rsv0_, MSW, NSB, PTV, HAV, HGV;
   int NPA, NPG;                       // bwgrad: 16-byte A / G staging loads per thread and tile
                                       // (register prefetch of the next tile); 0 = serial kernel
-  // wgrad8 (wgrad8.hip, v2 == 2): A image z-row stride (PA2 / PG2: plane
+  // wgrad8 (wgrad8.hip): A image z-row stride (PA2 / PG2: plane
   // strides), MFMA form (0: 16x16x4, 1: 4x4x1 16-block), voxel blocks per
   // instruction and z taps on the column side (form 1)
   int ARS, w8mode, w8nbv, w8nj, w8nh;
@@ -454,16 +453,32 @@ struct PwWgArgs {
 bool pw_wgrad_supported(int ACs, int GCs);
 int pw_wgrad_blocks(long nvox);
 int launch_pw_wgrad(const PwWgArgs &a, int blocks, hipStream_t s);
-// the row stride per tap of a weight-gradient slab (WGradFinalize::ACs)
-inline int wgrad_slab_acs(const WGradArgs &w) { return w.use_bw && w.ACr > 0 ? w.ACr : w.ACs; }
-int plan_bwgrad(WGradArgs &a, int target_blocks);
+int plan_bwgrad(WGradArgs &a);
 int launch_bwgrad(const WGradArgs &a, hipStream_t s);
-int plan_wgrad(WGradArgs &a, int target_blocks);
+// The generic tiling; wgrad3 / wgrad8 / wgrad2 re-plan a record that holds it
+// (they read CKA, CKG, MS, NS, mchunks, nchunks), size their own grids and
+// return 0 when they apply.
+int plan_wgrad_generic(WGradArgs &a, int target_blocks);
+int launch_wgrad_generic(const WGradArgs &a, hipStream_t s);
+int plan_wgrad2(WGradArgs &a);
+int launch_wgrad2(const WGradArgs &a, hipStream_t s);
 int plan_wgrad8(WGradArgs &a);
 int launch_wgrad8(const WGradArgs &a, hipStream_t s);
-int launch_wgrad(const WGradArgs &a, hipStream_t s);
-int plan_wgrad3(WGradArgs &a);                 // wgrad3.hip (v2 == 3)
+int plan_wgrad3(WGradArgs &a);
 int launch_wgrad3(const WGradArgs &a, hipStream_t s);
+// The weight-gradient families (families.cpp, as the convolutions').
+enum WGradKern { KWG_WGRAD = 0, KWG_WGRAD2, KWG_WGRAD8, KWG_WGRAD3, KWG_BWGRAD };
+struct WGradFamily {
+  const char *name;
+  int (*launch)(const WGradArgs &, hipStream_t);
+  bool real_rows;   // slab rows per tap: the real channels ACr (when set), not the stride ACs
+};
+const WGradFamily &wgrad_family(const WGradArgs &a);
+// Plans the weight gradient `a` of es-byte operands (4 fp32, 2 bf16).
+int plan_wgrad_any(WGradArgs &a, int es, int target_blocks);
+inline int launch_wgrad(const WGradArgs &a, hipStream_t s) { return wgrad_family(a).launch(a, s); }
+// the row stride per tap of a weight-gradient slab (WGradFinalize::ACs)
+inline int wgrad_slab_acs(const WGradArgs &w) { return wgrad_family(w).real_rows && w.ACr > 0 ? w.ACr : w.ACs; }
 inline size_t wgrad_partial_floats(const WGradArgs &a) {
   return (size_t)a.KB * a.Mtot * a.Ntot;
 }
@@ -596,44 +611,17 @@ int launch_from_cl(const float *xcl, float *x, int B, int C, int Cs, int64_t V,
 struct WPack {
   int on, CK, S, ICs, CoutW;
 };
-inline WPack wpack_of(const GConvArgs &a) {
-  WPack p{};
-  if (a.use_bconv && a.bes == 4) {   // fp32 bconv: the conv2 image [chunk][s][g][co][4]
-    const int T = a.KX * a.KY * a.KZ, TPS = 16 / a.CK;
-    p.on = 1;
-    p.CK = a.CK;
-    p.S = (T + TPS - 1) / TPS;
-    p.ICs = a.ICs;
-    p.CoutW = a.CoutW;
-    return p;
-  }
-  if (a.use_bconv) {   // bf16 image wg[chunk][s][g][co][8] (bconv.hip), 32 K per step
-    const int T = a.KX * a.KY * a.KZ, TPS = 32 / a.CK;
-    p.on = 3;
-    p.CK = a.CK;
-    p.S = (T + TPS - 1) / TPS;
-    p.ICs = a.ICs;
-    p.CoutW = a.CoutW;
-    return p;
-  }
-  if (a.use_conv8) {
-    p.on = 2;
-    p.CK = a.ICs / 4;
-    p.S = a.KX * a.KY * a.KZ;
-    p.ICs = a.ICs;
-    p.CoutW = 8;
-    return p;
-  }
-  if (!a.use_conv2) return p;
-  const int T = a.KX * a.KY * a.KZ, TPS = 16 / a.CK;
-  p.on = 1;
-  p.CK = a.CK;
-  p.S = (T + TPS - 1) / TPS;
-  p.ICs = a.ICs;
-  p.CoutW = a.CoutW;
-  return p;
+// on == 1 is also the fp32 bconv image; on == 3: the bf16 bconv image
+// wg[chunk][s][g][co][8], 32 K per step (TPS = 32/CK).
+// The image of packing `on` for the GEMM planned in `a`.
+inline WPack wpack_make(int on, const GConvArgs &a) {
+  const int T = a.KX * a.KY * a.KZ;
+  if (!on) return WPack{};
+  if (on == 2) return WPack{2, a.ICs / 4, T, a.ICs, 8};
+  const int TPS = (on == 3 ? 32 : 16) / a.CK;
+  return WPack{on, a.CK, (T + TPS - 1) / TPS, a.ICs, a.CoutW};
 }
-// Floats of the prepared weight buffer of a GEMM planned in `a`.
+inline WPack wpack_of(const GConvArgs &a) { return wpack_make(conv_family(a).wpack, a); }
 // Elements of a prepared weight buffer (plain [T][ICs][CoutW] when !on).
 __host__ __device__ inline int64_t wpack_count(const WPack &p, int T, int ICs, int CoutW) {
   if (p.on == 3) return (int64_t)p.ICs * p.S * (32 / p.CK) * p.CoutW;
@@ -641,15 +629,13 @@ __host__ __device__ inline int64_t wpack_count(const WPack &p, int T, int ICs, i
   if (p.on) return (int64_t)p.ICs * p.S * (16 / p.CK) * p.CoutW;
   return (int64_t)T * ICs * CoutW;
 }
-inline size_t wprep_floats(const GConvArgs &a) {
-  const int T = a.KX * a.KY * a.KZ;
-  if (a.use_bconv && a.bes == 4) return (size_t)wpack_count(wpack_of(a), T, a.ICs, a.CoutW);
-  if (a.use_bconv) return (size_t)(wpack_count(wpack_of(a), T, a.ICs, a.CoutW) + 1) / 2;
-  if (a.use_conv8) return (size_t)T * a.ICs * 8;
-  if (!a.use_conv2) return (size_t)T * a.ICs * a.CoutW;
-  const WPack p = wpack_of(a);
-  return (size_t)a.ICs * p.S * (16 / p.CK) * a.CoutW;
+// Elements of the weight image the GEMM planned in `a` reads, and the floats
+// an image of n elements of `bytes` each takes (the one place that sizes it).
+inline int64_t wimage_elems(const GConvArgs &a) {
+  return wpack_count(wpack_of(a), a.KX * a.KY * a.KZ, a.ICs, a.CoutW);
 }
+inline size_t wimage_floats(int64_t n, int bytes) { return ((size_t)n * bytes + 3) / 4; }
+inline size_t wprep_floats(const GConvArgs &a) { return wimage_floats(wimage_elems(a), conv_family(a).wbytes); }
 // Packed index -> (t, ci, co); false for a padded tap.  I = uint32_t where the
 // caller knows the image has < 2^31 elements (64-bit division is a ~100
 // instruction software sequence).

@@ -666,14 +666,6 @@ __global__ void __launch_bounds__(256) conv2_reduce_kernel(const GConvArgs a, in
 }
 
 // ---------------------------------------------------------------------------
-bool conv2_disabled() {
-  static const bool off = [] {
-    const char *e = getenv("HCU_NO_CONV2");
-    return e && e[0] == '1';
-  }();
-  return off;
-}
-
 static void tile2(int OX, int OY, int TZ, int maxM, int &TX, int &TY) {
   const int txy = std::max(1, maxM / TZ);
   TX = 1;
@@ -799,7 +791,7 @@ int plan_conv2(GConvArgs &a, int target_blocks) {
   if (a.nph == 1 && (a.CoutW / NT == 1 || a.OCs % NT == 0) && a.nc4 > 0 && 256 % a.nc4 == 0)
     a.epi_lds = 1;
   a.areg = (int)conv2_areg(a, a.CK, NT);
-  a.use_conv2 = 1;
+  a.kern = KCONV_CONV2;
   if (env_int("HCU_CONV2_LOG", 0))
     fprintf(stderr,
             "conv2 plan %d: B%d I%dx%dx%d ICs%d O%dx%dx%d S%dx%dx%d OCs%d Cout%d K%dx%dx%d s%d%d%d nph%d"
@@ -808,21 +800,6 @@ int plan_conv2(GConvArgs &a, int target_blocks) {
             a.KX, a.KY, a.KZ, a.sx, a.sy, a.sz, a.nph, a.CK, a.NSUB, a.MPW, a.TX, a.TY, a.TZ,
             a.ksplit, a.cps, a.NPF, a.gridx, a.epi_lds);
   return 0;
-}
-
-size_t conv2_partial_floats(const GConvArgs &a) {
-  return a.ksplit > 1 ? (size_t)a.ksplit * a.slice_floats : 0;
-}
-
-static int reduce_vox_per_block(const GConvArgs &a) { return 2 * 256 / (a.OCs / 4); }
-
-int conv2_stat_rows(const GConvArgs &a) {
-  if (a.ksplit > 1) {
-    const int64_t nvox = (int64_t)a.B * a.SX * a.SY * a.SZ;
-    const int vpb = reduce_vox_per_block(a);
-    return (int)((nvox + vpb - 1) / vpb);
-  }
-  return a.gridx;
 }
 
 #define CONV2_CASE(CK_, NS_, MP_, PF_)                                                         \
@@ -838,7 +815,7 @@ int conv2_stat_rows(const GConvArgs &a) {
 #define CONV2_NS(CK_) CONV2_MP(CK_, 1) else CONV2_MP(CK_, 2) else CONV2_MP(CK_, 4)
 
 int launch_conv2(const GConvArgs &a, hipStream_t s) {
-  const dim3 grid(a.gridx, a.CoutW / (a.NSUB * 16), a.ksplit);
+  const dim3 grid = conv2_grid(a);
   if (grid.y > 65535 || grid.z > 65535) return fail(4, "conv2: grid too large");
   if (a.ksplit > 1 && !a.partial) return fail(5, "conv2: K split needs a partial workspace");
   const double fl = a.flops > 0 ? a.flops
@@ -852,7 +829,7 @@ int launch_conv2(const GConvArgs &a, hipStream_t s) {
   HCU_CHECK_LAUNCH();
   if (a.ksplit > 1) {
     const int64_t nvox = (int64_t)a.B * a.SX * a.SY * a.SZ;
-    const int vpb = reduce_vox_per_block(a);
+    const int vpb = ksplit_vpb(a, 4);
     const int blocks = (int)((nvox + vpb - 1) / vpb);
     HCU_TIMED(s, "conv2_reduce_kernel", 0.0, 4.0 * (double)(a.ksplit + 1) * a.slice_floats,
               HCU_LAUNCH(conv2_reduce_kernel, dim3(blocks), dim3(256), 0, s, a, vpb));

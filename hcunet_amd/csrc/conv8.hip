@@ -57,14 +57,6 @@ __device__ unsigned long long g_conv8_phase[8192 * 8];
   } while (0)
 #endif
 
-bool conv8_disabled() {   // HCU_NO_CONV8=1 keeps the 16x16x4 kernels (A/B testing)
-  static const bool off = [] {
-    const char *e = getenv("HCU_NO_CONV8");
-    return e && e[0] == '1';
-  }();
-  return off;
-}
-
 // BNB: input gradient with the fused BatchNorm backward (a.bn_y set); a
 // template parameter so its loads never share registers or waits with the
 // forward epilogue.  INX (C4 == 1, forward): 0 = channels-last input; 1 / 2 /
@@ -516,8 +508,6 @@ static int env_npf_max() {
 // Chooses the tile, groups per wave and grid for conv8_kernel; non-zero when
 // the shape is not one conv8 handles (the caller then plans conv2 / gconv).
 int plan_conv8(GConvArgs &a, int target_blocks) {
-  a.use_conv8 = 0;
-  if (conv8_disabled()) return 1;
   if (a.nph > 1 || a.sx != 1 || a.sy != 1 || a.sz != 1) return 1;
   if (a.osx != 1 || a.osy != 1 || a.osz != 1 || a.ofx || a.ofy || a.ofz) return 1;
   if (a.Cout > 8 || a.OCs > 8 || a.ICs % 4 || a.KX * a.KY * a.KZ > 64) return 1;
@@ -587,8 +577,7 @@ int plan_conv8(GConvArgs &a, int target_blocks) {
   a.fKY = FastDiv(a.KY);
   const long tiles = (long)a.B * a.ntx * a.nty * a.ntz;
   a.gridx = (int)std::min<long>(tiles, 512L);   // two persistent workgroups per CU
-  a.use_conv8 = 1;
-  a.use_conv2 = 0;
+  a.kern = KCONV_CONV8;
   return 0;
 }
 
@@ -634,7 +623,7 @@ extern "C" int hcu_debug_conv8_phases(unsigned long long *out) {
 
 int launch_conv8(const GConvArgs &a, hipStream_t s) {
   const int C4 = a.ICs / 4;
-  if (a.in_fmt && (C4 != 1 || a.bn_y || a.in_scale || a.in_c < 1 || a.in_c > 4))
+  if (a.in_fmt && !(conv8_ncx_ok(a) && ncx_bound_ok(a)))
     return fail(4, "conv8: NCXYZ input needs a first-layer forward with <= 4 channels");
   const double fl = a.flops > 0 ? a.flops
                                 : 2.0 * a.B * a.OX * a.OY * a.OZ * (double)a.Cout * a.KX * a.KY *

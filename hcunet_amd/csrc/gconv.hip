@@ -247,6 +247,7 @@ static void tile_dims(int OX, int OY, int TZ, int maxM, int &TX, int &TY) {
 }
 
 int plan_gconv(GConvArgs &a, int target_blocks) {
+  a.kern = KCONV_GCONV;
   if (a.OX <= 0 || a.OY <= 0 || a.OZ <= 0) return fail(2, "gconv: empty output grid");
   if (a.ICs % 4 != 0 || a.OCs % 4 != 0) return fail(1, "gconv: channel strides must be multiples of 4");
   const int T = a.KX * a.KY * a.KZ;
@@ -333,7 +334,7 @@ static double gconv_bytes(const GConvArgs &a) {
 }
 
 int launch_gconv(const GConvArgs &a, hipStream_t s) {
-  const dim3 grid(a.ntx * a.nty * a.ntz, a.CoutW / (a.NSUB * 16), a.B);
+  const dim3 grid = gconv_grid(a);
   if (grid.y > 65535 || grid.z > 65535) return fail(4, "gconv: grid too large");
   GCONV_NS(4)
   GCONV_NS(8)

@@ -255,9 +255,8 @@ WGradArgs wgrad_conv(const Dims &in, const Dims &out, const int K[3], const int 
 // columns of real output channels only (WGradArgs::ACr / GCr): RDCNet's
 // 10-channel tensors sit in 16-slot strides.  Inputs made of channel parts
 // keep every packed slot (finalize maps torch channels to packed slots).
-void compact_slab(WGradArgs &w, const ConvLayer &L, bool bf) {
-  w.ACr = w.GCr = 0;
-  if (!bf) return;
+// (The fp32 planner clears both.)
+void compact_slab(WGradArgs &w, const ConvLayer &L) {
   if (L.part_c == 0 && L.groups == 1) w.ACr = L.E;
   w.GCr = L.Cout;
 }
@@ -285,7 +284,7 @@ void set_pw(ConvLayer &L, const Dims &in, int cin_total) {
          (!L.has_dgrad || pw_supported(in.Cs, L.out.Cs, L.Cout, true));
   // (the slab layout is bwgrad's taps_rows one, planned in L.wg)
   WGradJob &j = L.wg;
-  if (j.w.use_bw && j.w.taps_rows && j.w.ACs == in.Cs && j.w.GCs == L.out.Cs &&
+  if (j.w.taps_rows && j.w.ACs == in.Cs && j.w.GCs == L.out.Cs &&
       pw_wgrad_supported(in.Cs, L.out.Cs)) {
     j.pw_blocks = pw_wgrad_blocks(wgrad_gvox(j.w));
     j.pw_slab = (size_t)j.pw_blocks * j.w.Mtot * j.w.Ntot;
@@ -340,9 +339,6 @@ int setup_conv(ConvLayer &L, const Dims &in, int Cout, int groups, int fold_mod,
     o[i] = (span - 1) / L.S[i] + 1;
   }
   L.out = mkdims(in.B, o[0], o[1], o[2], Cout, in.es);
-  const bool bf = in.es == 2;
-  auto plan_c = [&](GConvArgs &a) { return bf ? plan_bconv(a, kTargetBlocks) : plan_conv_fp32(a, kTargetBlocks); };
-  auto plan_w = [&](WGradArgs &w) { return bf ? plan_bwgrad(w, kTargetBlocks) : plan_wgrad(w, kTargetBlocks); };
   L.has_dgrad = L.S[0] == 1 && L.S[1] == 1 && L.S[2] == 1;
   L.s2b = false;
   // direct form
@@ -350,7 +346,7 @@ int setup_conv(ConvLayer &L, const Dims &in, int Cout, int groups, int fold_mod,
     GConvArgs f = gconv_conv_fwd(in, L.out, L.K, L.D, Cout);
     f.sx = L.S[0]; f.sy = L.S[1]; f.sz = L.S[2];
     f.px = L.P[0]; f.py = L.P[1]; f.pz = L.P[2];
-    const int ef = plan_c(f);
+    const int ef = plan_conv(f, in.es, kTargetBlocks);
     if (ef && !sublattice) return ef;
     int ed = 0;
     GConvArgs dg{};
@@ -361,14 +357,14 @@ int setup_conv(ConvLayer &L, const Dims &in, int Cout, int groups, int fold_mod,
       dg.pz = L.D[2] * (L.K[2] - 1) - L.P[2];
       if (dg.px < 0 || dg.py < 0 || dg.pz < 0)
         return fail(HCU_ERR_UNSUPPORTED, std::string(name) + ": padding larger than dilation*(kernel-1)");
-      ed = plan_c(dg);
+      ed = plan_conv(dg, in.es, kTargetBlocks);
       if (ed && !sublattice) return ed;
     }
     WGradArgs w = wgrad_conv(in, L.out, L.K, L.D);
     w.asx = L.S[0]; w.asy = L.S[1]; w.asz = L.S[2];
     w.apx = L.P[0]; w.apy = L.P[1]; w.apz = L.P[2];
-    compact_slab(w, L, bf);
-    const int ew = plan_w(w);
+    compact_slab(w, L);
+    const int ew = plan_wgrad_any(w, in.es, kTargetBlocks);
     const bool dil = L.D[0] > 1 || L.D[1] > 1 || L.D[2] > 1;
     if (!ef && !ed && !ew) {
       L.fwd = f;
@@ -403,16 +399,16 @@ int setup_conv(ConvLayer &L, const Dims &in, int Cout, int groups, int fold_mod,
     L.sub_out = mkdims(in.B * nlat, sub_o[0], sub_o[1], sub_o[2], Cout, in.es);
     L.fwd = gconv_conv_fwd(L.sub_in, L.sub_out, L.K, one, Cout);
     L.fwd.px = Pd[0]; L.fwd.py = Pd[1]; L.fwd.pz = Pd[2];
-    if (int e = plan_c(L.fwd)) return e;
+    if (int e = plan_conv(L.fwd, in.es, kTargetBlocks)) return e;
     L.dgrad = gconv_conv_dgrad(L.sub_in, L.sub_out, L.K, one, L.E);
     L.dgrad.px = (L.K[0] - 1) - Pd[0];
     L.dgrad.py = (L.K[1] - 1) - Pd[1];
     L.dgrad.pz = (L.K[2] - 1) - Pd[2];
-    if (int e = plan_c(L.dgrad)) return e;
+    if (int e = plan_conv(L.dgrad, in.es, kTargetBlocks)) return e;
     WGradArgs w = wgrad_conv(L.sub_in, L.sub_out, L.K, one);
     w.apx = Pd[0]; w.apy = Pd[1]; w.apz = Pd[2];
-    compact_slab(w, L, bf);
-    if (int e = plan_w(w)) return e;
+    compact_slab(w, L);
+    if (int e = plan_wgrad_any(w, in.es, kTargetBlocks)) return e;
     L.wg = conv_wgrad_job(L, w);
   }
   L.bn.C = Cout;
@@ -472,11 +468,10 @@ int setup_convt(ConvTLayer &u, const Dims &cur, int o, const int K[3], const int
     // a lane's store span (zero weights and bias; RDCNet's 5 output channels)
     const int cv = bf ? 8 : 4;
     if (o % cv) a.cph = round_up(o, cv);
-    if (bf) {
-      if (int e = plan_bconv(a, kTargetBlocks)) return e;
-    } else if (plan_conv_fp32(a, kTargetBlocks) != 0 || !(a.use_bconv || a.use_conv2)) {
-      u.fused = false;
-    }
+    // (fp32: a shape no phase-folding family takes runs the per-phase form below)
+    const int e = plan_conv(a, cur.es, kTargetBlocks);
+    if (bf && e) return e;
+    if (e || !conv_family(a).folds_phases) u.fused = false;
     if (u.fused) {
       u.fwdf = a;
       need.conv(a);
@@ -500,7 +495,7 @@ int setup_convt(ConvTLayer &u, const Dims &cur, int o, const int K[3], const int
         a.sx = a.sy = a.sz = 1;
         a.dx = a.dy = a.dz = 1;
         a.px = Jx - 1; a.py = Jy - 1; a.pz = Jz - 1;
-        if (int e = plan_gconv(a, std::max(64, kTargetBlocks / nph))) return e;
+        if (int e = conv_family(KCONV_GCONV, 4).plan(a, std::max(64, kTargetBlocks / nph))) return e;
         u.phases.push_back(a);
         const int pj[6] = {qx, qy, qz, Jx, Jy, Jz};
         u.pJ.insert(u.pJ.end(), pj, pj + 6);
@@ -517,7 +512,7 @@ int setup_convt(ConvTLayer &u, const Dims &cur, int o, const int K[3], const int
     a.KX = u.K[0]; a.KY = u.K[1]; a.KZ = u.K[2];
     a.sx = u.S[0]; a.sy = u.S[1]; a.sz = u.S[2];
     a.dx = a.dy = a.dz = 1;
-    if (int e = bf ? plan_bconv(a, kTargetBlocks) : plan_conv_fp32(a, kTargetBlocks)) return e;
+    if (int e = plan_conv(a, cur.es, kTargetBlocks)) return e;
     u.dgrad = a;
     need.conv(a, 2);
   }
@@ -551,7 +546,7 @@ int setup_convt(ConvTLayer &u, const Dims &cur, int o, const int K[3], const int
     w.gdx = w.gdy = w.gdz = 1;
     w.taps_rows = 0;
     w.bias_row = 0;
-    if (int e = bf ? plan_bwgrad(w, kTargetBlocks) : plan_wgrad(w, kTargetBlocks)) return e;
+    if (int e = plan_wgrad_any(w, cur.es, kTargetBlocks)) return e;
     u.wg = wgrad_job(w, wgf(1, w));
     need.job(u.wg);
     // the bias gradient's channel-sum rows (layer chains: an arena slab)
@@ -582,7 +577,7 @@ int setup_convt(ConvTLayer &u, const Dims &cur, int o, const int K[3], const int
     w.taps_rows = 1;
     w.bias_row = 0;
     w.nph = nph; w.phx = u.S[0]; w.phy = u.S[1]; w.phz = u.S[2]; w.GCout = o;
-    if (plan_wgrad(w, kTargetBlocks) == 0 && w.v2 == 3) {
+    if (plan_wgrad_any(w, cur.es, kTargetBlocks) == 0 && w.kern == KWG_WGRAD3) {
       u.wgp = wgrad_job(w, wgf(3, w));
       need.job(u.wgp);
     } else {
@@ -608,7 +603,7 @@ int setup_convt(ConvTLayer &u, const Dims &cur, int o, const int K[3], const int
     v.ACr = u.Cout;
     v.GCr = u.Cin;
     v.flops = 2.0 * cur.B * u.in.X * u.in.Y * u.in.Z * (double)u.T * u.Cin * u.Cout;
-    if (plan_bwgrad(v, kTargetBlocks) == 0) {
+    if (plan_wgrad_any(v, cur.es, kTargetBlocks) == 0) {   // (swap: bf16 plans only)
       u.wgs = wgrad_job(v, wgf_conv(u.T, u.Cin, u.Cout, 1, u.Cout, 0, 0, wgrad_slab_acs(v)));
       need.job(u.wgs);
     } else {
@@ -736,12 +731,6 @@ struct hcu_unet_plan {
 
 namespace {
 
-// Elements of a prepared weight image (bf16 images hold two per float slot).
-size_t prep_elems(const GConvArgs &a) {
-  if (a.use_bconv) return (size_t)wpack_count(wpack_of(a), a.KX * a.KY * a.KZ, a.ICs, a.CoutW);
-  return wprep_floats(a);
-}
-
 void track_conv(hcu_unet_plan &p, const ConvLayer &L) {
   p.max_act = std::max(p.max_act, std::max(L.in.floats(), L.out.floats()));
   p.need.conv(L.fwd, 4);  // StatRow
@@ -757,8 +746,8 @@ void track_conv(hcu_unet_plan &p, const ConvLayer &L) {
 PrepJob prep_job(int kind, const GConvArgs &a, std::initializer_list<int> prm) {
   PrepJob j{};
   j.kind = kind;
-  j.bf16 = (a.use_bconv && a.bes != 4) ? 1 : 0;   // (every convolution of a bf16 plan)
-  j.n = (int64_t)prep_elems(a);
+  j.bf16 = conv_family(a).wbytes == 2;
+  j.n = wimage_elems(a);
   j.pk = wpack_of(a);
   std::copy(prm.begin(), prm.end(), j.p);
   return j;
@@ -798,7 +787,7 @@ PrepJob convt_dgrad_job(const ConvTLayer &u) {
 // of the weight at parameter offset `src`; off: its image in `saved`.
 void add_prep(hcu_unet_plan &p, Region &saved, PrepJob j, int64_t src, size_t &off) {
   j.src = src;
-  off = saved.take_floats(j.bf16 ? ((size_t)j.n + 1) / 2 : (size_t)j.n);
+  off = saved.take_floats(wimage_floats(j.n, j.bf16 ? 2 : 4));
   j.dst = (int64_t)(off / sizeof(float));
   p.prep_jobs.push_back(j);
 }
@@ -827,21 +816,41 @@ void split_prep(hcu_unet_plan &p) {
     (j.kind == PREP_CONV_DGRAD || j.kind == PREP_CONVT_DGRAD ? p.prep_bwd : p.prep_fwd).push_back(j);
 }
 
-// HCU_PLAN_LOG: the weight-gradient kernels with their partial slabs, and the
-// slab arena against the largest request it will get (measurement).
+// HCU_PLAN_LOG: the kernel family of every planned convolution with what it
+// asks of the workspaces, the weight-gradient kernels with their partial
+// slabs, and the slab arena against the largest request it will get
+// (measurement).
 void plan_log(const hcu_unet_plan &p) {
   if (!getenv("HCU_PLAN_LOG")) return;
+  auto clog = [](const std::string &n, const std::string &role, const GConvArgs &a) {
+    const dim3 g = conv_family(a).grid(a);
+    fprintf(stderr, "conv %-8s %-8s %-10s grid %u x %u x %u lds %d rows %d partial %zu wimage %zu\n", n.c_str(),
+            role.c_str(), conv_family(a).name, g.x, g.y, g.z, a.lds_bytes, gconv_rows(a), conv_partial_floats(a),
+            wprep_floats(a));
+  };
   auto wlog = [](const std::string &n, const WGradArgs &w) {
-    const char *k = w.use_bw ? "bwgrad" : w.v2 == 3 ? "wgrad3" : w.v2 == 2 ? "wgrad8" : w.v2 == 1 ? "wgrad2" : "wgrad";
-    fprintf(stderr, "wgrad %-8s %-7s KB %5d M %5d N %4d slabs %7.2f MB grid %d x %d x %d\n", n.c_str(), k,
-            w.KB, w.Mtot, w.Ntot, 4e-6 * w.KB * (double)w.Mtot * w.Ntot, w.KB, w.mchunks, w.nchunks);
+    fprintf(stderr, "wgrad %-8s %-7s KB %5d M %5d N %4d slabs %7.2f MB grid %d x %d x %d\n", n.c_str(),
+            wgrad_family(w).name, w.KB, w.Mtot, w.Ntot, 4e-6 * w.KB * (double)w.Mtot * w.Ntot, w.KB, w.mchunks,
+            w.nchunks);
+  };
+  auto conv_log = [&](const ConvLayer &cl) {
+    clog(cl.name, "fwd", cl.fwd);
+    if (cl.has_dgrad) clog(cl.name, "dgrad", cl.dgrad);
+    wlog(cl.name, cl.wg.w);
+  };
+  // (w: the weight-gradient form the executor runs)
+  auto convt_log = [&](const ConvTLayer &u, const WGradJob &w) {
+    if (u.fused) clog(u.name, "up.fwd", u.fwdf);
+    for (size_t ph = 0; !u.fused && ph < u.phases.size(); ++ph) clog(u.name, "ph" + std::to_string(ph), u.phases[ph]);
+    clog(u.name, "up.dgrad", u.dgrad);
+    wlog(u.name, w.w);
   };
   for (const auto *v : {&p.dc1, &p.dc2, &p.uc1, &p.uc2})
-    for (const ConvLayer &cl : *v) wlog(cl.name, cl.wg.w);
-  for (const ConvTLayer &u : p.up) wlog(u.name, u.wgp.on ? u.wgp.w : u.wg.w);
+    for (const ConvLayer &cl : *v) conv_log(cl);
+  for (const ConvTLayer &u : p.up) convt_log(u, u.wgp.on ? u.wgp : u.wg);
   for (const hcu_unet_plan::ChainOp &o : p.chain) {
-    if (o.kind == HCU_CHAIN_CONV) wlog(o.conv.name, o.conv.wg.w);
-    if (o.kind == HCU_CHAIN_CONVT) wlog(o.ct.name, o.ct.wgs.on ? o.ct.wgs.w : o.ct.wg.w);
+    if (o.kind == HCU_CHAIN_CONV) conv_log(o.conv);
+    if (o.kind == HCU_CHAIN_CONVT) convt_log(o.ct, o.ct.wgs.on ? o.ct.wgs : o.ct.wg);
   }
   // (a forward-only plan has no arena and runs no weight gradient)
   fprintf(stderr, "arena %zu largest slab %zu\n", p.wpart_floats,
@@ -1001,9 +1010,8 @@ int build_plan(hcu_unet_plan &p) {
     static const int ncx_env = getenv("HCU_NCX") ? (getenv("HCU_NCX")[0] == '1' ? 1 : 0) : -1;
     const bool ncx_on = ncx_env >= 0 ? ncx_env == 1 : p.es == 4;
     const GConvArgs &f = p.dc1[0].fwd;
-    const bool conv8_ok = f.use_conv8 && f.ICs == 4 && p.es == 4;
-    const bool bconv_ok = f.use_bconv && f.CK == (p.es == 2 ? 8 : 4) && f.NPF > 0 && f.ksplit == 1 && f.nph <= 1;
-    p.ncx_first = ncx_on && s.in_channels <= 4 && s.g1 == 1 && (conv8_ok || bconv_ok);
+    const auto ncx_ok = conv_family(f).ncx_ok;
+    p.ncx_first = ncx_on && s.in_channels <= 4 && s.g1 == 1 && ncx_ok && ncx_ok(f);
   }
   p.outd = mkdims(p.B, cur.X, cur.Y, cur.Z, p.Co, 4);
   {
@@ -1286,7 +1294,7 @@ int conv_forward(const Ctx &c, const ConvLayer &L, const float *in, const float 
 // planned kernel cannot.
 bool fuse_bnbwd(Ctx &c, GConvArgs &a, const ConvLayer *bnl) {
   static const bool off = getenv("HCU_NO_BNFUSE") != nullptr;   // A/B debugging
-  if (off || !bnl || !conv_bnbwd_fusable(a)) return false;
+  if (off || !bnl || !conv_family(a).bnbwd) return false;
   const BNCoef coef = coef_at(c.sv, bnl->bn);
   a.bn_y = c.fptr(c.sv, bnl->y_off);
   a.bn_scale = coef.scale;
@@ -1307,11 +1315,6 @@ int finish_bn(const Ctx &c, const ConvLayer &bnl, int R, int W, float *dz, int t
   return launch_bn_bwd_apply(dz, c.fptr(c.sv, bnl.y_off), coef, bnl.out.vox(), bnl.out.Cs, c.s, c.bf());
 }
 
-int finish_bnbwd(const Ctx &c, const GConvArgs &a, const ConvLayer &bnl, float *dz, int training,
-                 int accumulate) {
-  return finish_bn(c, bnl, gconv_rows(a), a.CoutW, dz, training, accumulate);
-}
-
 // Input gradient dP of the ConvTranspose3d `u` from dU.  With `bnl`, the
 // layer that produced u's input, its BatchNorm+ReLU backward is fused into the
 // kernel where the planned one can (fuse_bnbwd): dP then leaves as bnl's
@@ -1323,7 +1326,7 @@ int convt_dgrad(Ctx &c, const ConvTLayer &u, const float *dU, float *dP, const C
   if (int e = launch_conv_any(a, c.s)) return e;
   if (!fused) return 0;
   tag(bnl->name, "bnbwd");
-  return finish_bnbwd(c, a, *bnl, dP, training, accumulate);
+  return finish_bn(c, *bnl, gconv_rows(a), a.CoutW, dP, training, accumulate);
 }
 
 // Weight/bias gradient and (optionally) input gradient of one Conv3d layer.
@@ -1417,7 +1420,7 @@ int conv_backward(Ctx &c, const ConvLayer &L, const float *A, const float *asc,
     if (int e = conv_wgrad(c, L, A, asc, ash, dy, dy_slot, accumulate)) return e;
   if (!fused) return 0;
   tag(bnl->name, "bnbwd");
-  if (int e = finish_bnbwd(c, a, *bnl, dA, training, accumulate)) return e;
+  if (int e = finish_bn(c, *bnl, gconv_rows(a), a.CoutW, dA, training, accumulate)) return e;
   if (bn_done) *bn_done = true;
   return 0;
 }

@@ -17,14 +17,6 @@
 
 namespace hcu {
 
-bool wgrad2_disabled() {   // HCU_NO_WGRAD2=1 forces the generic kernel (A/B testing)
-  static const bool off = [] {
-    const char *e = getenv("HCU_NO_WGRAD2");
-    return e && e[0] == '1';
-  }();
-  return off;
-}
-
 template <int NS, int MSMAX>
 __global__ void __launch_bounds__(256) wgrad_kernel(const WGradArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -480,8 +472,8 @@ __global__ void __launch_bounds__(256) wgrad2_kernel(const WGradArgs a) {
 
 // Re-plans a Conv3d wgrad (taps_rows, stride-1 operands) for wgrad2_kernel:
 // tile, padded LDS images, persistent grid.  Returns 0 when wgrad2 applies.
-static int plan_wgrad2(WGradArgs &a, int target_blocks) {
-  a.v2 = 0;
+int plan_wgrad2(WGradArgs &a) {
+  a.kern = KWG_WGRAD;
   // (the ConvTranspose3d phase form: A zero-padded, G strided by the phases)
   const bool ph = a.nph > 1;
   if (!a.taps_rows || a.asx != 1 || a.asy != 1 || a.asz != 1 || a.gpx || a.gpy || a.gpz ||
@@ -542,13 +534,13 @@ static int plan_wgrad2(WGradArgs &a, int target_blocks) {
   long kb = std::max(1L, 192L * a.occ / per);
   kb = std::min(kb, total);
   a.KB = (int)kb;
-  a.v2 = 1;
-  (void)target_blocks;
+  a.kern = KWG_WGRAD2;
   return 0;
 }
 
-int plan_wgrad(WGradArgs &a, int target_blocks) {
+int plan_wgrad_generic(WGradArgs &a, int target_blocks) {
   const int T = a.KX * a.KY * a.KZ;
+  a.kern = KWG_WGRAD;
   a.ACr = a.GCr = 0;   // (bwgrad only)
   if (a.ACs % 4 || a.GCs % 4) return fail(1, "wgrad: channel strides must be multiples of 4");
   if (a.PX <= 0 || a.PY <= 0 || a.PZ <= 0) return fail(2, "wgrad: empty grid");
@@ -652,43 +644,35 @@ int plan_wgrad(WGradArgs &a, int target_blocks) {
   long kb = std::max(1L, (long)target_blocks * side_cus() / 256 / per);
   kb = std::min(kb, total);
   a.KB = (int)kb;
-  if (plan_wgrad3(a) == 0) return 0;   // deep layers / ConvTranspose3d phase form: the output-split form
-  if (a.nph > 1) {   // the phase form runs on wgrad2 only
-    if (wgrad2_disabled() || plan_wgrad2(a, target_blocks) != 0)
-      return fail(4, "wgrad: no wgrad2 tile for the ConvTranspose3d phase form");
-    return 0;
-  }
-  if (plan_wgrad8(a) != 0 && !wgrad2_disabled()) plan_wgrad2(a, target_blocks);
   return 0;
 }
 
-int launch_wgrad(const WGradArgs &a, hipStream_t s) {
-  if (a.use_bw) return launch_bwgrad(a, s);
-  if (a.v2 == 2) return launch_wgrad8(a, s);
-  if (a.v2 == 3) return launch_wgrad3(a, s);
+int launch_wgrad2(const WGradArgs &a, hipStream_t s) {
   const dim3 grid(a.KB, a.mchunks, a.nchunks);
   const int T = a.KX * a.KY * a.KZ;
-  if (a.v2) {
-    const double fl2 = a.flops > 0 ? a.flops
-                                   : 2.0 * a.B * a.PX * a.PY * a.PZ * (double)T * a.ACs * a.GCs;
-    const double by2 = 4.0 * ((double)a.B * a.AX * a.AY * a.AZ * a.ACs +
-                              (double)a.B * a.GX * a.GY * a.GZ * a.GCs);
-    bool ok = false;
+  const double fl2 = a.flops > 0 ? a.flops : 2.0 * a.B * a.PX * a.PY * a.PZ * (double)T * a.ACs * a.GCs;
+  const double by2 = 4.0 * ((double)a.B * a.AX * a.AY * a.AZ * a.ACs +
+                            (double)a.B * a.GX * a.GY * a.GZ * a.GCs);
+  bool ok = false;
 #define W2(NS_, MS_)                                                                       \
   if (!ok && a.NS == NS_ && a.MS == MS_) {                                                 \
     HCU_TIMED(s, "wgrad2_kernel<" #NS_ "," #MS_ ">", fl2, by2,                              \
               HCU_LAUNCH((wgrad2_kernel<NS_, MS_>), grid, dim3(256), a.lds_bytes, s, a)); \
     ok = true;                                                                             \
   }
-    W2(1, 1) W2(1, 2) W2(1, 3) W2(1, 4) W2(1, 5) W2(1, 6) W2(1, 7) W2(1, 8)
-    W2(1, 9) W2(1, 10) W2(1, 11) W2(1, 12) W2(1, 13) W2(1, 14) W2(1, 15) W2(1, 16)
-    W2(2, 1) W2(2, 2) W2(2, 3) W2(2, 4) W2(2, 5) W2(2, 6) W2(2, 7) W2(2, 8)
-    W2(4, 1) W2(4, 2) W2(4, 3) W2(4, 4)
+  W2(1, 1) W2(1, 2) W2(1, 3) W2(1, 4) W2(1, 5) W2(1, 6) W2(1, 7) W2(1, 8)
+  W2(1, 9) W2(1, 10) W2(1, 11) W2(1, 12) W2(1, 13) W2(1, 14) W2(1, 15) W2(1, 16)
+  W2(2, 1) W2(2, 2) W2(2, 3) W2(2, 4) W2(2, 5) W2(2, 6) W2(2, 7) W2(2, 8)
+  W2(4, 1) W2(4, 2) W2(4, 3) W2(4, 4)
 #undef W2
-    if (!ok) return fail(4, "wgrad2: unsupported variant");
-    HCU_CHECK_LAUNCH();
-    return 0;
-  }
+  if (!ok) return fail(4, "wgrad2: unsupported variant");
+  HCU_CHECK_LAUNCH();
+  return 0;
+}
+
+int launch_wgrad_generic(const WGradArgs &a, hipStream_t s) {
+  const dim3 grid(a.KB, a.mchunks, a.nchunks);
+  const int T = a.KX * a.KY * a.KZ;
   const double fl = a.flops > 0 ? a.flops
                                 : 2.0 * a.B * a.PX * a.PY * a.PZ * (double)T * a.ACs * a.GCs;
   const double by = 4.0 * ((double)a.B * a.AX * a.AY * a.AZ * a.ACs +

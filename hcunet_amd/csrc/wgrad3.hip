@@ -28,14 +28,6 @@
 
 namespace hcu {
 
-bool wgrad3_enabled() {   // HCU_WGRAD3=0 keeps the deep layers on wgrad2 (A/B)
-  static const bool on = [] {
-    const char *e = getenv("HCU_WGRAD3");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 constexpr int kW3Loads = 8;   // 16-byte staging loads in flight per thread (serial staging)
 
 template <int MS, int NS>
@@ -295,7 +287,7 @@ static int cm_stride(int n) { return n + ((2 - n % 32) + 32) % 32; }
 // bytes a cycle) + its slab write, the blocks spread over the 192 CUs the branch
 // stream is sized for.
 int plan_wgrad3(WGradArgs &a) {
-  if (!wgrad3_enabled() || !a.taps_rows) return 1;
+  if (!a.taps_rows) return 1;
   const bool ph = a.nph > 1;   // ConvTranspose3d phase form: A padded, G strided by the phases
   if (a.asx != 1 || a.asy != 1 || a.asz != 1 || a.gpx || a.gpy || a.gpz) return 1;
   if (!ph && (a.apx || a.apy || a.apz || a.gsx != 1 || a.gsy != 1 || a.gsz != 1)) return 1;
@@ -403,13 +395,13 @@ int plan_wgrad3(WGradArgs &a) {
           c.fHAY = FastDiv(HAY);
           c.fTY = FastDiv(TY);
           c.fTZ = FastDiv(TZP);   // G tile z rows (the staging's voxel decode)
-          c.v2 = 3;
+          c.kern = KWG_WGRAD3;
           bestA = c;
         }
       }
     }
   }
-  if (bestA.v2 != 3) return 1;
+  if (bestA.kern != KWG_WGRAD3) return 1;   // no candidate
   a = bestA;
   a.Mtot = T * a.ACs + (a.bias_row ? 1 : 0);
   a.Ntot = ncols;

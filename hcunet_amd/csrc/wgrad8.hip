@@ -378,7 +378,6 @@ static bool w8_nr_supported(int mode, int nr) {
 
 // Re-plans a Conv3d weight gradient for wgrad8_kernel; returns 0 when it applies.
 int plan_wgrad8(WGradArgs &a) {
-  if (getenv("HCU_NO_WGRAD8") && getenv("HCU_NO_WGRAD8")[0] == '1') return 1;
   if (!a.taps_rows || a.asx != 1 || a.asy != 1 || a.asz != 1 || a.gsx != 1 || a.gsy != 1 ||
       a.gsz != 1 || a.apx || a.apy || a.apz || a.gpx || a.gpy || a.gpz)
     return 1;
@@ -531,7 +530,7 @@ int plan_wgrad8(WGradArgs &a) {
     }
   }
   a.KB = (int)std::max(1L, best_kb);
-  a.v2 = 2;
+  a.kern = KWG_WGRAD8;
   return 0;
 }
 

@@ -156,7 +156,7 @@ int main(int argc, char **argv) {
     a.bn_invstd = dev_fill((size_t)a.OCs, hco);
   }
   if (!dgrad || bnbwd) {
-    const size_t rows = (size_t)bconv_stat_rows(a);
+    const size_t rows = (size_t)ksplit_stat_rows(a, 16 / ES);
     CK_HIP(hipMalloc(&a.stats, rows * a.CoutW * 4 * sizeof(float)));
   }
   if (a.ksplit > 1) CK_HIP(hipMalloc(&a.partial, (size_t)a.ksplit * a.slice_floats * sizeof(float)));
