@@ -20,6 +20,8 @@ HCU_ERR_UNSUPPORTED = 4
 HCU_ERR_WORKSPACE = 5
 
 HCU_F32, HCU_F16, HCU_U8, HCU_BF16, HCU_U16, HCU_F64 = 0, 1, 2, 3, 4, 5
+HCU_I32, HCU_U32 = 6, 7
+PWL_MAX_RADIUS, PWL_MAX_OFFSETS, MOMENT_LDS_IDS = 9, 9 * 63, 256
 HCU_PLAN_FORWARD_ONLY = 1
 HCU_TILE_BATCH_MAX = 64
 MAX_LEVELS = 12
@@ -236,6 +238,13 @@ SYMBOLS = [
     ("hcu_tile_scatter", _I, [_VP, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), _VP,
                               _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), _I,
                               _F, _VP]),
+    ("hcu_label_keys", _I, [_VP, _I, _I, _I, _I, _I, _I, _VP, _VP]),
+    ("hcu_pwl_scan", _I, [_VP, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I),
+                          ctypes.POINTER(ctypes.c_double), _VP, _VP]),
+    ("hcu_label_moments", _I, [_VP, _I, _I, _I, _I, _VP, _VP]),
+    ("hcu_center_table", _I, [_VP, _I, _I, _I, _I, _I, _VP, _VP, _VP]),
+    ("hcu_vector_to_center", _I, [_VP, _I, _I, _I, _VP, _I, _VP, _VP]),
+    ("hcu_colormask_binary", _I, [_VP, _I, _I, _I, _I, _VP, _VP]),
     ("hcu_timing_enable", _I, [_I]),
     ("hcu_timing_disable", _I, []),
     ("hcu_timing_detail", _I, [_I]),

@@ -20,9 +20,13 @@ errors and __getitem__ order of transforms as the reference.  What changes:
   converted by one hcu_ingest_jobs launch on a side stream.
 Files are read with skimage.io.imread (as the reference) or tifffile when
 importable; `reader=` takes any callable path -> ndarray.
+
+RecursiveStack (hcat/dataloader.py:190-278) is the same loader with two more
+volumes per item, the centre-of-mass stack and the unpickled vector field.
 """
 import glob
 import os
+import pickle
 
 import numpy as np
 import torch
@@ -196,8 +200,9 @@ class Stack(torch.utils.data.Dataset):
         for i in items:   # RNG draws in item order, to_tensor's joint seed included: the stream of self[i]
             vols.append([t._wrap(x) for x in self._recorded(i)])
             np.random.randint(0, 1e8, 1)
+        n = len(vols[0])   # 3 volumes per item; RecursiveStack: 5
         outs = []
-        for k in range(3):
+        for k in range(n):
             shapes = [v[k].shape for v in vols]
             if any(len(s) != 4 for s in shapes):
                 raise ValueError(f'Stack.batches expects [x,y,z,c] volumes, got {shapes} for items {items}')
@@ -206,8 +211,8 @@ class Stack(torch.utils.data.Dataset):
                                  + ', '.join(f'item {i}: {s}' for i, s in zip(items, shapes)))
             X, Y, Z, C = shapes[0]
             outs.append(_lib.empty((len(items), C, X, Y, Z), torch.float16, device))
-        flat = [v[k] for v in vols for k in range(3)]
-        t.materialise_many(flat, [outs[k][b] for b in range(len(items)) for k in range(3)], device)
+        flat = [v[k] for v in vols for k in range(n)]
+        t.materialise_many(flat, [outs[k][b] for b in range(len(items)) for k in range(n)], device)
         return tuple(outs)
 
     def batches(self, batch_size, order=None, device=None):
@@ -240,3 +245,65 @@ class Stack(torch.utils.data.Dataset):
             for x in out:
                 x.record_stream(main)
             yield out
+
+
+class RecursiveStack(Stack):
+    """Drop-in hcat.dataloader.RecursiveStack (hcat/dataloader.py:190-278), the
+    dataloader of hcat.r_unet: per `*.mask.tif` also `.labels.com.tif` (kept
+    with a channel axis, :243) and the unpickled `.labels.vector.pkl`; items
+    are (image, mask, pwl, com, vec).  Same constructor, file discovery and
+    __getitem__ order (joint, image, out transforms) as the reference, and a
+    stack whose files are incomplete is reported and skipped the same way: the
+    message is printed and the lists go on (:245-246).  `reader=`,
+    `resident_bytes=`, `prefetch` and `batches` as Stack; the five volumes go
+    through the lazy device chain, the float64 `vec` by hcu_ingest_volume."""
+
+    def __init__(self, path, image_transforms, joint_transforms, out_transforms=None, reader=None,
+                 resident_bytes=None):
+        self.resident_left = float('inf') if resident_bytes is None else int(resident_bytes)
+        if out_transforms is None:
+            out_transforms = [t.to_tensor()]
+        self.image_transforms = image_transforms
+        self.out_transforms = out_transforms
+        self.joint_transforms = joint_transforms
+        self.files = glob.glob(f'{path}{os.sep}*.mask.tif')
+        if len(self.files) == 0:
+            raise FileExistsError('No Valid Mask Files Found')
+        reader = reader or _default_reader()
+        if reader is None:
+            raise ImportError('hcat.dataloader.RecursiveStack reads .tif stacks with skimage.io or tifffile; '
+                              'neither is installed (pass reader=callable)')
+        self.image, self.mask, self.pwl, self.com, self.vec = [], [], [], [], []
+        for mask_path in self.files:
+            try:
+                base = os.path.splitext(os.path.splitext(mask_path)[0])[0]
+                self.image.append(_Raw(reader(base + '.tif'), self))
+                m = reader(mask_path)
+                try:   # some masks are [Z,Y,X,C], others [Z,Y,X] (:237-240)
+                    m = m[:, :, :, 0]
+                except IndexError:
+                    pass
+                self.mask.append(_Raw(m, self))
+                self.pwl.append(_Raw(reader(base + '.pwl.tif'), self))
+                self.com.append(_Raw(reader(base + '.labels.com.tif')[:, :, :, np.newaxis], self))
+                with open(base + '.labels.vector.pkl', 'rb') as f:
+                    self.vec.append(_Raw(pickle.load(f), self))
+            except FileNotFoundError:
+                print(f'ISSUE WITH: {os.path.splitext(mask_path)[0]}')
+
+    def _recorded(self, item):
+        """The joint and image transforms of one item (:257-274)."""
+        vols = [self.image[item].pending(), self.mask[item].pending(expand=True),
+                self.pwl[item].pending(expand=True), self.com[item].pending(), self.vec[item].pending()]
+        for jt in self.joint_transforms:
+            vols = list(jt(_arrays_for(jt, vols)))
+        for it in self.image_transforms:
+            vols[0] = it(_arrays_for(it, [vols[0]])[0])
+        return tuple(vols)
+
+    def __getitem__(self, item):
+        image, mask, pwl, com, vec = self._recorded(item)
+        for ot in self.out_transforms:
+            image, mask, pwl, com, vec = _arrays_for(ot, [image, mask, pwl, com, vec])
+            image, mask, pwl, com, vec = ot([image, mask, pwl, com, vec])
+        return image, mask, pwl, com, vec

@@ -62,7 +62,8 @@ enum {
   HCU_ERR_WORKSPACE = 5    /* workspace too small */
 };
 
-enum { HCU_F32 = 0, HCU_F16 = 1, HCU_U8 = 2, HCU_BF16 = 3, HCU_U16 = 4, HCU_F64 = 5 };
+enum { HCU_F32 = 0, HCU_F16 = 1, HCU_U8 = 2, HCU_BF16 = 3, HCU_U16 = 4, HCU_F64 = 5,
+       HCU_I32 = 6, HCU_U32 = 7 /* label ids (training targets) */ };
 
 const char *hcu_last_error(void);
 int hcu_version(void);
@@ -545,6 +546,57 @@ int hcu_tile_gather(const void *image, int image_dtype, int C, int X, int Y, int
 int hcu_tile_scatter(const float *out, const int *out_dims, const int *crop_lo, const int *bcast,
                      void *mask, int mask_dtype, const int *mask_dims, const int *dst_lo,
                      const int *write_dims, int threshold, float thr, hcu_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* Training targets from instance labels (hcat/train/train_utils.py: makePWL
+ * :9-93, colormask_to_mask :175-187, CalculateCenterOfMass :190-237,
+ * VectorToCenter :240-274).  Stacks are [Z][Y][X] (colour stacks
+ * [Z][Y][X][3]) with Z*Y*X < 2^31 (HCU_ERR_UNSUPPORTED beyond); results are
+ * integers, table values or one float64 division of exact integers, so they
+ * are bitwise the reference's.  Every output element is written.            */
+/* ------------------------------------------------------------------------ */
+#define HCU_PWL_MAX_RADIUS 9
+#define HCU_PWL_MAX_OFFSETS (9 * 63)
+#define HCU_MOMENT_LDS_IDS 256 /* ids accumulated in LDS by hcu_label_moments */
+/* keys[v] = one 64-bit key per voxel: channels 3 (dtype HCU_U8 / HCU_U16),
+ * (c0 << 32) | (c1 << 16) | c2, so numeric key order is the lexicographic
+ * colour order of np.unique(axis=0); channels 1 (HCU_U8 / HCU_U16 / HCU_I32 /
+ * HCU_U32, ids not negative), the id.  map_first != 0: keys equal to voxel
+ * 0's become 0 (set_background, :228-237).  Key 0 is background. */
+int hcu_label_keys(const void *labels, int dtype, int Z, int Y, int X, int channels, int map_first,
+                   uint64_t *keys, hcu_stream_t stream);
+/* out[z][y][x] (float64) = makePWL.find_closest (:62-93): 0 where the key is
+ * not 0; else the voxel probes, in the same slice, keys[z][y + dy][x + dx]
+ * (0 outside the stack: the reference's zero padding) over radii l = 1..9 in
+ * order and the offsets of a radius in order; the first key != 0 fixes
+ * (closest, l0), the first later key != 0 and != closest fixes l1, and the
+ * value is values[(l0 - 1) * 9 + (l1 - 1)], or 0 when either is missing.
+ * HOST arrays, copied into the launch: offsets [ring_begin[9]][2] of (dx, dy),
+ * each within [-9, 9]; ring_begin [10] ascending from 0 to at most
+ * HCU_PWL_MAX_OFFSETS (radius l owns [ring_begin[l-1], ring_begin[l]));
+ * values [81] (HCU_ERR_INVALID otherwise). */
+int hcu_pwl_scan(const uint64_t *keys, int Z, int Y, int X, const int *offsets, const int *ring_begin,
+                 const double *values, double *out, hcu_stream_t stream);
+/* moments[id] = {count, sum z, sum y, sum x} over the voxels of each id in
+ * [0, n_ids) (voxels with any other value are skipped); moments: [n_ids][4],
+ * cleared by the call.  Exact, order-free integer sums. */
+int hcu_label_moments(const int32_t *ids, int Z, int Y, int X, int n_ids, uint64_t *moments,
+                      hcu_stream_t stream);
+/* For each id in [1, n_ids): count[id] = voxels of `center` (HCU_F64, HCU_U8,
+ * HCU_U16, HCU_I32 or HCU_U32) equal to id, index[id] = the largest linear
+ * index of one, or -1.  index, count: [n_ids], entry 0 is -1 / 0. */
+int hcu_center_table(const void *center, int dtype, int Z, int Y, int X, int n_ids, int32_t *index,
+                     int32_t *count, hcu_stream_t stream);
+/* out[z][y][x][0..2] (float64) = ((z - cz) / Z, (y - cy) / Y, (x - cx) / X)
+ * with (cz, cy, cx, use) = centres[4 * id .. 4 * id + 3] (16-byte aligned) of
+ * the voxel's id; 0 for id 0, ids outside [0, n_ids) and ids whose `use` is 0. */
+int hcu_vector_to_center(const int32_t *ids, int Z, int Y, int X, const int32_t *centres, int n_ids,
+                         double *out, hcu_stream_t stream);
+/* colormask [Z][Y][X][3] (HCU_U8 / HCU_U16 / HCU_I32 / HCU_U32), in place: a
+ * voxel with any channel != 0 becomes (1, 1, 1); mask[z][y][x] (uint8) =
+ * channel 0 * 255. */
+int hcu_colormask_binary(void *colormask, int dtype, int Z, int Y, int X, uint8_t *mask,
+                         hcu_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* Measurement: opt-in HIP-event timing of every library launch (bench.py). */
