@@ -1,5 +1,8 @@
 """hcat.segment: re-export of the MI355X-native tiled inference driver
-(hcunet_amd/segment.py; reference hcat/segment.py:21-136).  Only
-predict_segmentation_mask is on the hot path; the watershed/RCNN
-post-processing of the reference module is out of scope."""
+(hcunet_amd/segment.py; reference hcat/segment.py:21-136) and of RDCNet's
+post-processing, vector field to instance labels (hcunet_amd/instances.py;
+reference :563-658): pixel_vec_to_cell and hist3d.  The watershed / RCNN
+post-processing of the reference module stays out of scope:
+skimage's watershed is a sequential priority flood."""
+from hcunet_amd.instances import hist3d, pixel_vec_to_cell  # noqa: F401
 from hcunet_amd.segment import predict_segmentation_mask  # noqa: F401

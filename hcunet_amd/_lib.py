@@ -22,6 +22,7 @@ HCU_ERR_WORKSPACE = 5
 HCU_F32, HCU_F16, HCU_U8, HCU_BF16, HCU_U16, HCU_F64 = 0, 1, 2, 3, 4, 5
 HCU_I32, HCU_U32 = 6, 7
 PWL_MAX_RADIUS, PWL_MAX_OFFSETS, MOMENT_LDS_IDS = 9, 9 * 63, 256
+VOTE_RADIUS = 20
 HCU_PLAN_FORWARD_ONLY = 1
 HCU_TILE_BATCH_MAX = 64
 MAX_LEVELS = 12
@@ -245,6 +246,12 @@ SYMBOLS = [
     ("hcu_center_table", _I, [_VP, _I, _I, _I, _I, _I, _VP, _VP, _VP]),
     ("hcu_vector_to_center", _I, [_VP, _I, _I, _I, _VP, _I, _VP, _VP]),
     ("hcu_colormask_binary", _I, [_VP, _I, _I, _I, _I, _VP, _VP]),
+    ("hcu_vec_votes", _I, [_VP, _I, _I64, _I, _I, _I, _I, _VP, _VP, _VP]),
+    ("hcu_vote_hist", _I, [_VP, _VP, _I, _I, _I, _VP, _VP]),
+    ("hcu_vote_smooth", _I, [_VP, _VP, _I, _I, _I, ctypes.POINTER(ctypes.c_double), _I, _VP, _VP, _VP]),
+    ("hcu_smooth_f64", _I, [_VP, _I, _I, _I, ctypes.POINTER(ctypes.c_double), _I, _VP, _VP, _VP]),
+    ("hcu_peak_candidates", _I, [_VP, _I, _I, _I, _VP, _VP, _I, _VP, ctypes.POINTER(_I), _VP]),
+    ("hcu_vec_label", _I, [_VP, _I, _I64, _I, _I, _I, _VP, _I, _VP, _I, _I, _VP, _VP]),
     ("hcu_timing_enable", _I, [_I]),
     ("hcu_timing_disable", _I, []),
     ("hcu_timing_detail", _I, [_I]),

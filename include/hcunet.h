@@ -599,6 +599,59 @@ int hcu_colormask_binary(void *colormask, int dtype, int Z, int Y, int X, uint8_
                          hcu_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
+/* Instance labels from RDCNet's vector field (hcat/segment.py:
+ * pixel_vec_to_cell :563-628, hist3d :631-658).  Volumes are [X][Y][Z], Z
+ * contiguous, X*Y*Z < 2^31 (HCU_ERR_UNSUPPORTED beyond).  vec: three channel
+ * planes [X][Y][Z] of HCU_F32 / HCU_F16 / HCU_BF16, plane c at vec +
+ * c * chan_stride elements (chan_stride >= X*Y*Z: a channel slice of a
+ * network output is read in place).  The voxel (x, y, z) points at
+ * c = (x + v2, y + v1, z + v0), fp32: the channel order is reversed.
+ * Integer atomics only; every float result is bitwise the reference's.     */
+/* ------------------------------------------------------------------------ */
+#define HCU_VOTE_RADIUS 20 /* taps of hcu_vote_smooth on each side of the centre */
+/* counts[floor(c)] += 1 for every voxel whose floor(c) lies inside the volume
+ * (compared in fp32; a non-finite component is skipped); max_count[0] =
+ * max(max_count[0], largest count).  counts [X*Y*Z] and max_count [1] must be
+ * ZERO on entry: the call adds to them.  points != 0: the planes hold the
+ * points themselves, c = (plane 0, plane 1, plane 2), and no position is
+ * added (hist3d's own argument). */
+int hcu_vec_votes(const void *vec, int dtype, int64_t chan_stride, int points, int X, int Y, int Z,
+                  uint32_t *counts, uint32_t *max_count, hcu_stream_t stream);
+/* hist[v] (float64) = (1 + counts[v]) / (1 + max_count[0]): hist3d's result. */
+int hcu_vote_hist(const uint32_t *counts, const uint32_t *max_count, int X, int Y, int Z, double *hist,
+                  hcu_stream_t stream);
+/* out = gaussian_filter(maximum_filter(hist, size=2, mode='constant'),
+ * mode='nearest') of the hist above, float64, over axes 0, 1, 2 in that
+ * order.  weights: HOST array [radius + 1], weights[radius] the centre tap,
+ * weights[radius - i] the taps at distance i; radius in [0, HCU_VOTE_RADIUS].
+ * Each pass sums as scipy's symmetric correlate1d does, t = in[l] * w[r], then
+ * for i = r .. 1: t += (in[l-i] + in[l+i]) * w[r-i], indices clamped to the
+ * edge, without contraction.  scratch: X*Y*Z float64; out and scratch are
+ * both written whole. */
+int hcu_vote_smooth(const uint32_t *counts, const uint32_t *max_count, int X, int Y, int Z,
+                    const double *weights, int radius, double *out, double *scratch, hcu_stream_t stream);
+/* The same three passes over a float64 volume `in` (no maximum filter):
+ * stage 3 alone.  in, out and scratch are distinct. */
+int hcu_smooth_f64(const double *in, int X, int Y, int Z, const double *weights, int radius, double *out,
+                   double *scratch, hcu_stream_t stream);
+/* Peak candidates of h (float64, no NaN): voxels off the outermost layer of
+ * every axis that equal the maximum of their 3x3x3 neighbourhood and are
+ * > min(h).  cand_index[k] (linear index) and cand_value[k] for k <
+ * min(*n_found, capacity), in no particular order; *n_found (HOST) = the
+ * number found.  state: 4 device words the call owns.  The call WAITS for the
+ * stream.  More than `capacity` candidates: HCU_ERR_WORKSPACE, *n_found set. */
+int hcu_peak_candidates(const double *h, int X, int Y, int Z, int32_t *cand_index, double *cand_value,
+                        int capacity, uint32_t *state, int *n_found, hcu_stream_t stream);
+/* label[v] (float64) = label_offset + i of the first peak i (peaks: device
+ * int32 [n][3], n >= 0) whose fp32 distance sqrt((c0-p0)^2 + (c1-p1)^2 +
+ * (c2-p2)^2) to the voxel's c is strictly below every earlier peak's and
+ * below 100000; 0 where none is, and 0 where float(mask[v]) < 0.2 (mask:
+ * [X][Y][Z] of HCU_U8, HCU_F32, HCU_F16, HCU_BF16 or HCU_F64; null: no mask). */
+int hcu_vec_label(const void *vec, int dtype, int64_t chan_stride, int X, int Y, int Z, const int32_t *peaks,
+                  int n, const void *mask, int mask_dtype, int label_offset, double *label,
+                  hcu_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
 /* Measurement: opt-in HIP-event timing of every library launch (bench.py). */
 /* ------------------------------------------------------------------------ */
 int hcu_timing_enable(int max_launches);
