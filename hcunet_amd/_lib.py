@@ -23,6 +23,7 @@ HCU_F32, HCU_F16, HCU_U8, HCU_BF16, HCU_U16, HCU_F64 = 0, 1, 2, 3, 4, 5
 HCU_I32, HCU_U32 = 6, 7
 PWL_MAX_RADIUS, PWL_MAX_OFFSETS, MOMENT_LDS_IDS = 9, 9 * 63, 256
 VOTE_RADIUS = 20
+BOX_LDS_IDS, CELL_MAX_PLANES = 256, 1024
 HCU_PLAN_FORWARD_ONLY = 1
 HCU_TILE_BATCH_MAX = 64
 MAX_LEVELS = 12
@@ -252,6 +253,8 @@ SYMBOLS = [
     ("hcu_smooth_f64", _I, [_VP, _I, _I, _I, ctypes.POINTER(ctypes.c_double), _I, _VP, _VP, _VP]),
     ("hcu_peak_candidates", _I, [_VP, _I, _I, _I, _VP, _VP, _I, _VP, ctypes.POINTER(_I), _VP]),
     ("hcu_vec_label", _I, [_VP, _I, _I64, _I, _I, _I, _VP, _I, _VP, _I, _I, _VP, _VP]),
+    ("hcu_cell_boxes", _I, [_VP, _I, _I, _I, _I, _VP, _VP]),
+    ("hcu_cell_stats", _I, [_VP, _VP, _VP, _I, _I64, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hcu_timing_enable", _I, [_I]),
     ("hcu_timing_disable", _I, []),
     ("hcu_timing_detail", _I, [_I]),

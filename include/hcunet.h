@@ -652,6 +652,41 @@ int hcu_vec_label(const void *vec, int dtype, int64_t chan_stride, int X, int Y,
                   hcu_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
+/* Cell objects from a label volume (hcat/segment.py: generate_cell_objects
+ * :508-560; hcat/haircell.py: HairCell :5-85).  ids: int32 [X][Y][Z], Z
+ * contiguous, X*Y*Z < 2^31 (HCU_ERR_UNSUPPORTED beyond), values in
+ * [0, n_ids); a voxel with any other value belongs to no id.                */
+/* ------------------------------------------------------------------------ */
+#define HCU_BOX_LDS_IDS 256      /* ids whose box hcu_cell_boxes keeps in LDS */
+#define HCU_CELL_MAX_PLANES 1024 /* largest Z of hcu_cell_stats               */
+/* boxes[id] = {x0, y0, z0, x1, y1, z1}: the inclusive minimum and maximum
+ * index of the id's voxels along each axis; all six are -1 for an id without
+ * a voxel.  boxes: [n_ids][6], every word written.  Integer atomics only. */
+int hcu_cell_boxes(const int32_t *ids, int X, int Y, int Z, int n_ids, int32_t *boxes, hcu_stream_t stream);
+/* Per id in [1, n_ids) and channel c < C, over the id's CLIPPED box x0:x1,
+ * y0:y1, z0:z1 of `boxes` (the maximum face of every axis dropped, as the
+ * reference slices; a box is first held inside the volume).  image: C channel
+ * volumes [X][Y][Z] of HCU_F32 / HCU_F16 / HCU_BF16, channel c at image +
+ * c * chan_stride elements (chan_stride >= X*Y*Z).  Z <= HCU_CELL_MAX_PLANES.
+ *   count[id]           voxels of the id in the clipped box
+ *   plane_count[id][z]  the same per z plane of the volume (0 outside z0:z1)
+ *   box_min[id]         minimum of the clipped box over all C channels and all
+ *                       its voxels, the id's or not; NaN when it holds a NaN,
+ *                       +inf when it is empty
+ *   g                   the channel's values at the id's voxels as float32,
+ *                       mapped to g * 0.5f + 0.5f when box_min[id] < 0
+ *   mean[id][c]         float64 sum of g / count
+ *   std[id][c]          sqrt(sum((g - mean)^2) / count), float64
+ *   median[id][c][0..1] the order statistics floor((count - 1) / 2) and
+ *                       floor(count / 2) of g (-0 sorts below +0)
+ * mean, std and median are NaN where count <= 1 or g holds a NaN.  Row 0 of
+ * every table is written as an empty cell's.  The sums are reduced in a fixed
+ * order: the same input gives the same bits in every call. */
+int hcu_cell_stats(const int32_t *ids, const int32_t *boxes, const void *image, int dtype, int64_t chan_stride,
+                   int C, int X, int Y, int Z, int n_ids, int32_t *count, int32_t *plane_count, float *box_min,
+                   double *mean, double *std, float *median, hcu_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
 /* Measurement: opt-in HIP-event timing of every library launch (bench.py). */
 /* ------------------------------------------------------------------------ */
 int hcu_timing_enable(int max_launches);
