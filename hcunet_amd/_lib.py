@@ -253,6 +253,8 @@ SYMBOLS = [
     ("hcu_smooth_f64", _I, [_VP, _I, _I, _I, ctypes.POINTER(ctypes.c_double), _I, _VP, _VP, _VP]),
     ("hcu_peak_candidates", _I, [_VP, _I, _I, _I, _VP, _VP, _I, _VP, ctypes.POINTER(_I), _VP]),
     ("hcu_vec_label", _I, [_VP, _I, _I64, _I, _I, _I, _VP, _I, _VP, _I, _I, _VP, _VP]),
+    ("hcu_vec_label_paste", _I, [_VP, _I, _I64, _I, _I, _I, _VP, _VP, _I, _VP, _I, ctypes.POINTER(_F), _VP,
+                                 _I, _I, _I, _I, _I, _I, _VP]),
     ("hcu_cell_boxes", _I, [_VP, _I, _I, _I, _I, _VP, _VP]),
     ("hcu_cell_stats", _I, [_VP, _VP, _VP, _I, _I64, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hcu_timing_enable", _I, [_I]),

@@ -6,6 +6,8 @@
 //   hcu_smooth_f64       the Gaussian alone
 //   hcu_peak_candidates  the local-maximum test of peak_local_max (:605)
 //   hcu_vec_label        nearest peak of every voxel's vote, masked (:609-626)
+//   hcu_vec_label_paste  the same winner for one window of a tiled stack, renumbered to a
+//                        stack-wide id and written into the stack's int32 label volume
 // Volumes are [X][Y][Z] with Z contiguous; consecutive lanes run along Z.
 // Votes and the candidate list use integer atomics only (exact, order-free);
 // the float work is one IEEE division of exact integers, fp64 multiply / add
@@ -39,6 +41,15 @@ constexpr int kVoteSlots = 1024;           // a workgroup's LDS vote table (8 KB
 constexpr int kVoteProbes = 8;             // slots tried before a vote goes straight to global memory
 constexpr uint32_t kVoteChunk = 4096;      // voxels per workgroup (at least)
 constexpr uint32_t kNoVoxel = 0xFFFFFFFFu; // (a voxel index is below 2^31)
+constexpr int kPeakSlots = 1024;           // peaks a workgroup of the paste pass keeps in LDS (16 KB)
+
+struct alignas(16) PeakSlot {
+  float p0, p1, p2;   // the peak, as the distance reads it
+  int32_t id;         // its stack-wide id, 0: not this window's
+};
+struct VoteBounds {
+  float lo[3], hi[3];   // floor(c) must lie in [lo, hi) on every axis
+};
 
 struct SmoothTaps {
   double w[HCU_VOTE_RADIUS + 1];   // w[k]: the tap at distance k
@@ -274,6 +285,64 @@ vec_label_kernel(const void *vec, int dtype, int64_t cs, uint32_t nvox, FastDiv 
   }
 }
 
+// vec_label_kernel's winner per voxel of one window of a larger volume, renumbered through `ids` and
+// written into that volume at the window's origin.  A voxel is written only where a peak won, its id
+// is not 0, the mask keeps it and floor(c) lies inside the vote bounds; every other destination voxel
+// is left as it was.  The first kPeakSlots peaks are staged once per workgroup as floats next to
+// their ids (one 16-byte LDS read per peak, the same address in every lane); any further ones are read
+// from global memory at a wave-uniform index.  (float)peak is exact either way: same bits.
+__global__ void __launch_bounds__(256)
+vec_label_paste_kernel(const void *vec, int dtype, int64_t cs, uint32_t nvox, FastDiv fZ, FastDiv fY,
+                       const int32_t *__restrict__ peaks, const int32_t *__restrict__ ids, int n, const void *mask,
+                       int mask_dtype, const VoteBounds vb, int32_t *dst, int DY, int DZ, int ox, int oy, int oz) {
+#pragma clang fp contract(off)
+  __shared__ PeakSlot table[kPeakSlots];
+  const int staged = n < kPeakSlots ? n : kPeakSlots;
+  for (int k = threadIdx.x; k < staged; k += 256) {
+    PeakSlot p;
+    p.p0 = (float)peaks[3 * k];
+    p.p1 = (float)peaks[3 * k + 1];
+    p.p2 = (float)peaks[3 * k + 2];
+    p.id = ids[k];
+    table[k] = p;
+  }
+  __syncthreads();
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nvox; i += gridDim.x * 256u) {
+    int q, x, y, z;
+    fZ.divmod(i, q, z);
+    fY.divmod((uint32_t)q, x, y);
+    float c0, c1, c2;
+    vote_of(vec, dtype, cs, i, x, y, z, c0, c1, c2);
+    float nearest = kFarthest;
+    int id = 0;   // nothing below 100000, or a winner that another window owns: no write
+    for (int k = 0; k < staged; ++k) {
+      const PeakSlot p = table[k];
+      const float d0 = c0 - p.p0, d1 = c1 - p.p1, d2 = c2 - p.p2;
+      const float d = sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
+      if (nearest > d) {   // strict, and false for a NaN distance
+        nearest = d;
+        id = p.id;
+      }
+    }
+    for (int k = staged; k < n; ++k) {   // (uniform index: every lane reads the same peak)
+      const float d0 = c0 - (float)peaks[3 * k], d1 = c1 - (float)peaks[3 * k + 1],
+                  d2 = c2 - (float)peaks[3 * k + 2];
+      const float d = sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
+      if (nearest > d) {
+        nearest = d;
+        id = ids[k];
+      }
+    }
+    if (id == 0) continue;
+    if (mask && load_as_float(mask, mask_dtype, i) < 0.2f) continue;
+    const float f0 = floorf(c0), f1 = floorf(c1), f2 = floorf(c2);
+    // compared as floats against bounds that may be +-Inf; a NaN or Inf vote has no winner above
+    if (!(f0 >= vb.lo[0] && f0 < vb.hi[0] && f1 >= vb.lo[1] && f1 < vb.hi[1] && f2 >= vb.lo[2] && f2 < vb.hi[2]))
+      continue;
+    dst[((size_t)(ox + x) * (size_t)DY + (size_t)(oy + y)) * (size_t)DZ + (size_t)(oz + z)] = id;
+  }
+}
+
 static int volume_voxels(const char *what, int X, int Y, int Z, uint32_t *nvox) {
   if (X <= 0 || Y <= 0 || Z <= 0) return fail(HCU_ERR_SHAPE, std::string(what) + ": empty volume");
   const int64_t n = (int64_t)X * Y * Z;
@@ -462,6 +531,40 @@ extern "C" int hcu_vec_label(const void *vec, int dtype, int64_t chan_stride, in
             HCU_LAUNCH(vec_label_kernel, dim3(voxel_grid(nvox)), dim3(256), 0, s, vec, dtype, chan_stride, nvox,
                        FastDiv((uint32_t)Z), FastDiv((uint32_t)Y), peaks, n, mask, mask_dtype, label_offset,
                        label));
+  HCU_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int hcu_vec_label_paste(const void *vec, int dtype, int64_t chan_stride, int X, int Y, int Z,
+                                   const int32_t *peaks, const int32_t *ids, int n, const void *mask,
+                                   int mask_dtype, const float *bounds, int32_t *dst, int DX, int DY, int DZ,
+                                   int ox, int oy, int oz, hcu_stream_t stream) {
+  if (!dst || !bounds) return fail(HCU_ERR_INVALID, "vec_label_paste: null argument");
+  uint32_t nvox, ndst;
+  if (int rc = volume_voxels("vec_label_paste", X, Y, Z, &nvox)) return rc;
+  if (int rc = volume_voxels("vec_label_paste destination", DX, DY, DZ, &ndst)) return rc;
+  if (int rc = vector_ok("vec_label_paste", vec, dtype, chan_stride, nvox)) return rc;
+  if (n < 0 || (n > 0 && (!peaks || !ids)))
+    return fail(HCU_ERR_INVALID, "vec_label_paste: n peaks need a peak table and an id table");
+  if (mask && mask_dtype != HCU_U8 && mask_dtype != HCU_F32 && mask_dtype != HCU_F16 && mask_dtype != HCU_BF16 &&
+      mask_dtype != HCU_F64)
+    return fail(HCU_ERR_INVALID, "vec_label_paste: the mask is uint8, fp32, fp16, bf16 or float64");
+  VoteBounds vb;
+  for (int a = 0; a < 3; ++a) {
+    vb.lo[a] = bounds[2 * a];
+    vb.hi[a] = bounds[2 * a + 1];
+    if (std::isnan(vb.lo[a]) || std::isnan(vb.hi[a]))
+      return fail(HCU_ERR_INVALID, "vec_label_paste: a vote bound is NaN");
+  }
+  if (ox < 0 || oy < 0 || oz < 0 || (int64_t)ox + X > DX || (int64_t)oy + Y > DY || (int64_t)oz + Z > DZ)
+    return fail(HCU_ERR_SHAPE, "vec_label_paste: the window does not lie inside the destination");
+  if (n == 0) return 0;   // no peak: nothing wins, nothing is written
+  hipStream_t s = (hipStream_t)stream;
+  const double es = dtype == HCU_F32 ? 4.0 : 2.0;
+  HCU_TIMED(s, "vec_label_paste_kernel", (double)nvox * 9.0 * n, (double)nvox * (3.0 * es + 5.0),
+            HCU_LAUNCH(vec_label_paste_kernel, dim3(voxel_grid(nvox)), dim3(256), 0, s, vec, dtype, chan_stride,
+                       nvox, FastDiv((uint32_t)Z), FastDiv((uint32_t)Y), peaks, ids, n, mask, mask_dtype, vb, dst,
+                       DY, DZ, ox, oy, oz));
   HCU_CHECK_LAUNCH();
   return 0;
 }

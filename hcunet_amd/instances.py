@@ -43,6 +43,14 @@ stage 4, e.g. skimage's own peak_local_max result; num_peaks, sigma
 (radius int(4 * sigma + 0.5) <= 20), label_offset.  The reference's two shape
 prints are dropped, its count line is kept.  A batch other than 1 raises
 ValueError (the reference's squeeze(0) then fails on a shape mismatch).
+
+Whole stacks (no counterpart in the reference, whose RDCNet code only ever
+sees one training crop): windows() cuts a stack into cores with clipped halos,
+stitch_vec_to_cell runs stages 1-4 per window and hcu_vec_label_paste, which
+fuses stage 5 with the renumbering to stack-wide ids and the write into one
+int32 label volume (the rule: stitch_vec_to_cell's docstring, DESIGN.md §3);
+paste_window is the per-window step hcunet_amd.segment.predict_instance_mask
+shares.
 """
 import ctypes
 
@@ -254,6 +262,150 @@ def hist3d(mat):
     return out if isinstance(mat, torch.Tensor) else out.cpu().numpy()
 
 
+def _check_mask(mask, shape, what):
+    mask = _as_tensor(mask)
+    if mask.dim() == 5:
+        mask = mask[0, 0]
+    if tuple(int(s) for s in mask.shape) != shape:
+        raise ValueError(f'{what}: mask {tuple(mask.shape)} does not match the volume {shape}')
+    if mask.dtype not in _MASK_CODES:
+        raise TypeError(f'{what}: the mask is bool, uint8 or floating, got {mask.dtype}')
+    return mask
+
+
+def windows(shape, tile, halo):
+    """The windows of a tiled stack `shape` = (X, Y, Z), a list of dicts with
+    core_lo, core_hi, lo, hi (3-tuples, half-open).  On every axis the cores
+    are [k * tile, min((k + 1) * tile, n)), a partition; a window is its core
+    grown by `halo` on both sides and clipped to [0, n) (clipped, not
+    reflected: a mirrored halo would hold mirror-image cells).  tile[a] None:
+    the whole axis.  x is the slowest index of the list and z the fastest;
+    this is the order of the launches and of the ids."""
+    shape = tuple(int(n) for n in shape)
+    if len(shape) != 3 or len(tile) != 3 or len(halo) != 3:
+        raise ValueError('windows: shape, tile and halo have three entries each')
+    if min(shape) < 1:
+        raise ValueError(f'windows: empty volume {shape}')
+    axes = []
+    for n, t, h in zip(shape, tile, halo):
+        t = n if t is None else int(t)
+        h = int(h)
+        if t <= 0:
+            raise ValueError(f'windows: tile sizes are positive, got {tuple(tile)}')
+        if h < 0:
+            raise ValueError(f'windows: halos are not negative, got {tuple(halo)}')
+        axes.append([(c, min(c + t, n), max(c - h, 0), min(min(c + t, n) + h, n)) for c in range(0, n, t)])
+    return [dict(core_lo=(x[0], y[0], z[0]), core_hi=(x[1], y[1], z[1]), lo=(x[2], y[2], z[2]),
+                 hi=(x[3], y[3], z[3])) for x in axes[0] for y in axes[1] for z in axes[2]]
+
+
+def vote_bounds(window, shape):
+    """Rule (d) of the stitch as six floats {lo0, hi0, lo1, hi1, lo2, hi2}:
+    floor(c) of a written voxel keeps one voxel off every face of the window
+    that is not a face of the volume; a face of the volume is open (+-Inf)."""
+    out = []
+    for a in range(3):
+        w = window['hi'][a] - window['lo'][a]
+        out += [1.0 if window['lo'][a] > 0 else -np.inf, float(w - 1) if window['hi'][a] < shape[a] else np.inf]
+    return np.array(out, dtype=np.float32)
+
+
+def owned_ids(peaks, window, first_id):
+    """(int32 [n] ids, int64 [m,3] stack-wide positions of the owned peaks):
+    a peak is owned when window lo + peak lies inside the window's core; owned
+    peaks take first_id, first_id + 1, ... in peak order, the others 0."""
+    pos = np.asarray(peaks, dtype=np.int64).reshape(-1, 3) + np.asarray(window['lo'], dtype=np.int64)
+    own = np.all((pos >= np.asarray(window['core_lo'])) & (pos < np.asarray(window['core_hi'])), axis=1)
+    ids = np.zeros(len(pos), dtype=np.int32)
+    ids[own] = first_id + np.arange(int(own.sum()), dtype=np.int32)
+    return ids, pos[own]
+
+
+def paste_window(t, code, stride, mask, window, labels, first_id, sigma=5, num_peaks=NUM_PEAKS):
+    """One window of the stitch: stages 1-4 on the window's planes (_planes()),
+    then paste_peaks."""
+    wshape = tuple(int(s) for s in t.shape[1:])
+    h = _Votes(t, code, stride).smooth(sigma)
+    peaks = select_peaks(*peak_candidates(h), wshape, num_peaks)
+    return paste_peaks(t, code, stride, mask, peaks, window, labels, first_id)
+
+
+def paste_peaks(t, code, stride, mask, peaks, window, labels, first_id):
+    """hcu_vec_label_paste of one window into `labels` (int32 [X,Y,Z] device
+    tensor of the whole stack).  t, code, stride: the window's planes
+    (_planes()); mask: the window's, a contiguous device tensor; peaks: the
+    window's, int [n,3] in window-local coordinates.  Returns the stack-wide
+    positions of the peaks this window owns, int64 [m,3]; their ids are
+    first_id .. first_id + m - 1."""
+    wshape = tuple(int(s) for s in t.shape[1:])
+    ids, centres = owned_ids(peaks, window, first_id)
+    n = len(peaks)
+    if not ids.any():
+        return centres          # no peak of this window's own: nothing would be written
+    table = _lib.empty((4 * n,), torch.int32, t.device)   # the peaks [n,3], then their ids [n]
+    table.copy_(torch.from_numpy(np.concatenate([peaks.astype(np.int32).reshape(-1), ids])))
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    bounds = vote_bounds(window, tuple(int(s) for s in labels.shape))
+    X, Y, Z = wshape
+    DX, DY, DZ = (int(s) for s in labels.shape)
+    with torch.cuda.device(t.device):
+        _lib.check(_lib.lib().hcu_vec_label_paste(
+            _lib.ptr(t), code, stride, X, Y, Z, _lib.ptr(table), _lib.ptr(table[3 * n:]), n, _lib.ptr(mask),
+            _MASK_CODES[mask.dtype], bounds.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), _lib.ptr(labels),
+            DX, DY, DZ, *window['lo'], _lib.stream_handle(t.device)), 'vec_label_paste')
+    return centres
+
+
+def stitch_vec_to_cell(vector, mask, *, tile, halo, sigma=5, num_peaks=NUM_PEAKS, as_tensor=False):
+    """Instance labels of a whole stack from its vector field, window by
+    window: (labels int32 [X,Y,Z], centres int64 [n,3]); row g - 1 of centres
+    is the stack-wide position of id g.  vector [1,3,X,Y,Z] and mask as
+    pixel_vec_to_cell takes them, on the host or the device; as_tensor=True
+    returns the labels as a device tensor.
+
+    For each window of windows(shape, tile, halo), in order: stages 1-4 of
+    pixel_vec_to_cell on the window's crop (window-local coordinates; sigma
+    and num_peaks are per window); a peak is owned by the window whose core
+    holds it and owned peaks take consecutive ids from 1; a voxel is written
+    with its nearest peak's id where a peak won, float(mask) >= 0.2, the id is
+    not 0 and floor of its own vote keeps one voxel off every interior face of
+    the window (vote_bounds: the layer where no peak is ever reported); a
+    later window overwrites an earlier one, unwritten voxels stay 0.  One
+    window over the whole volume gives int32(pixel_vec_to_cell(...,
+    label_offset=1)).  A cell is whole only if it fits into core + halo of the
+    window that owns it; a peak that two windows place in different cores is
+    doubled or lost."""
+    what = 'stitch_vec_to_cell'
+    shape = _field_shape(vector, what)
+    mask = _check_mask(mask, shape, what)
+    wins = windows(shape, tile, halo)
+    device = _device_of(vector, mask)
+    v = _as_tensor(vector)[0]
+    if v.dtype == torch.float64:
+        v = v.float()
+    if v.dtype not in _VEC_CODES:
+        raise TypeError(f'{what}: the vector field is fp32, fp16 or bf16, got {v.dtype}')
+    v, mask = v.to(device), mask.to(device)
+    labels = torch.zeros(shape, dtype=torch.int32, device=device)
+    centres = []
+    count = 0
+    for w in wins:
+        box = tuple(slice(a, b) for a, b in zip(w['lo'], w['hi']))
+        wshape = tuple(b - a for a, b in zip(w['lo'], w['hi']))
+        crop = _lib.empty((3,) + wshape, v.dtype, device)
+        crop.copy_(v[(slice(None),) + box])
+        mcrop = _lib.empty(wshape, mask.dtype, device)
+        mcrop.copy_(mask[box])
+        t, code, stride = _planes(crop, device, what)
+        got = paste_window(t, code, stride, mcrop, w, labels, count + 1, sigma, num_peaks)
+        centres.append(got)
+        count += len(got)
+    print(f'Predicted {count} cell from runet output')
+    centres = np.concatenate(centres).reshape(-1, 3) if centres else np.zeros((0, 3), dtype=np.int64)
+    return (labels if as_tensor else labels.cpu().numpy()), centres
+
+
 def pixel_vec_to_cell(vector, mask, *, as_tensor=False, peaks=None, num_peaks=NUM_PEAKS, sigma=5,
                       label_offset=0):
     """pixel_vec_to_cell(vector, mask) -> float64 [X,Y,Z]: the index of the
@@ -261,13 +413,7 @@ def pixel_vec_to_cell(vector, mask, *, as_tensor=False, peaks=None, num_peaks=NU
     fp16 / bf16, mask [1,1,X,Y,Z] or [X,Y,Z] bool / uint8 / floating, on the
     host or the device."""
     shape = _field_shape(vector, 'pixel_vec_to_cell')
-    mask = _as_tensor(mask)
-    if mask.dim() == 5:
-        mask = mask[0, 0]
-    if tuple(int(s) for s in mask.shape) != shape:
-        raise ValueError(f'pixel_vec_to_cell: mask {tuple(mask.shape)} does not match the volume {shape}')
-    if mask.dtype not in _MASK_CODES:
-        raise TypeError(f'pixel_vec_to_cell: the mask is bool, uint8 or floating, got {mask.dtype}')
+    mask = _check_mask(mask, shape, 'pixel_vec_to_cell')
     if peaks is not None:
         peaks = np.asarray(peaks)
         if peaks.ndim != 2 or peaks.shape[1] != 3 or peaks.dtype.kind not in 'iu':

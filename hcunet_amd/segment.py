@@ -27,16 +27,23 @@ messages as the reference; what changes is where the work runs:
 Deliberate difference: the reference cleans NaN/Inf *in the caller's tensor*
 (segment.py:66-67 assigns into ``image``); this driver leaves the caller's
 tensor untouched and cleans on the fly.
+
+``predict_instance_mask`` is the same kind of driver for RDCNet (no
+counterpart in the reference, whose RDCNet code only ever sees one training
+crop): windows with a clipped halo, one batched forward per run of equal
+windows, and each window's cells written into one int32 label volume with
+stack-wide ids (``instances.paste_window``; the rule is in
+``instances.stitch_vec_to_cell`` and DESIGN.md §3).
 """
 import ctypes
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, instances
 
-__all__ = ['predict_segmentation_mask', 'pad_image_with_reflections', 'calculate_indexes',
-           'eval_image_size', 'PAD_SIZE']
+__all__ = ['predict_segmentation_mask', 'predict_instance_mask', 'pad_image_with_reflections',
+           'calculate_indexes', 'eval_image_size', 'PAD_SIZE']
 
 # hcat/segment.py:48-57
 _EVAL_IM_SIZE = {'4': [128, 128, 6],   # In GB
@@ -159,6 +166,95 @@ def _tile_bytes(unet, C, tdims):
     plan = eng.plan((1, C) + tuple(tdims), unet._bf16(), forward_only=True)
     out = 4 * plan.out_shape[1] * plan.out_shape[2] * plan.out_shape[3] * plan.out_shape[4]
     return 4 * C * vox + out + plan.saved_bytes + plan.scratch_bytes
+
+
+def _oom(e):
+    return isinstance(e, torch.OutOfMemoryError) or 'out of memory' in str(e)
+
+
+def predict_instance_mask(model, image, *, tile=(384, 384, None), halo=(64, 64, 0), mask_threshold=0.5,
+                          sigma=5, num_peaks=instances.NUM_PEAKS, tiles_per_batch=None):
+    """Instance labels of a whole stack from RDCNet: (labels int32
+    [1,1,X,Y,Z] on the device, centres int64 [n,3] on the host, row g - 1 the
+    position of id g).  image: [1,C,X,Y,Z], any device, copied to HBM once.
+
+    The stack is cut into instances.windows(shape, tile, halo) (cores of
+    `tile` grown by `halo`, clipped at the faces: 512 x 512 x Z by default).
+    Each window is cropped on the device and run through `model` under
+    torch.no_grad(); out[b, 0] > mask_threshold is its mask and out[b, 2:5]
+    its vector field, read in place (the reference's
+    pixel_vec_to_cell(out[:, 2:], out[0, 0] > 0.5)); instances.paste_window
+    labels it and writes its cells into the one label volume by the rule of
+    instances.stitch_vec_to_cell (num_peaks and sigma are per window).
+    Windows of equal shape share a forward in eval mode, as
+    predict_segmentation_mask batches its tiles (tiles_per_batch bounds it; the
+    default is what fits a quarter of free memory, halved on out-of-memory);
+    in train mode they run one by one.
+
+    RDCNet's stride-2 convolution and stride-2 ConvTranspose3d give back the
+    input size for even sizes only, so odd X / Y / Z, tile or halo entries are
+    a ValueError.  An output with fewer than 5 channels or another shape than
+    its window is a RuntimeError."""
+    if not isinstance(image, torch.Tensor):
+        image = torch.as_tensor(image)
+    if image.dim() != 5 or image.shape[0] != 1:
+        raise ValueError(f'predict_instance_mask: expected a [1,C,X,Y,Z] image, got {tuple(image.shape)}')
+    shape = tuple(int(s) for s in image.shape[2:])
+    for what, vals in (('image size', shape), ('tile', tile), ('halo', halo)):
+        if any(v is not None and int(v) % 2 for v in vals):
+            raise ValueError(f'predict_instance_mask: {what} {tuple(vals)} has an odd entry; the stride-2 '
+                             'convolution and transposed convolution return the input size for even sizes '
+                             'only: crop the image (image[..., :-1]) and use even tiles and halos')
+    wins = instances.windows(shape, tile, halo)
+    dev = _device()
+    vol = image if image.dtype in (torch.float32, torch.float16, torch.bfloat16) else image.float()
+    vol = vol.to(dev)
+    C = int(vol.shape[1])
+    labels = torch.zeros(shape, dtype=torch.int32, device=dev)
+    batch_cap = 1 if model.training else _lib.HCU_TILE_BATCH_MAX
+    if tiles_per_batch is not None:
+        batch_cap = max(1, min(batch_cap, int(tiles_per_batch)))
+
+    def dims(w):
+        return tuple(b - a for a, b in zip(w['lo'], w['hi']))
+
+    centres, count, i = [], 0, 0
+    with torch.no_grad():
+        while i < len(wins):
+            wdims = dims(wins[i])
+            j = i + 1
+            cap = batch_cap
+            if tiles_per_batch is None and cap > 1:
+                free = torch.cuda.mem_get_info(dev)[0]
+                cap = max(1, min(cap, int(free / 4 // _tile_bytes(model, C, wdims))))
+            while j < len(wins) and j - i < cap and dims(wins[j]) == wdims:
+                j += 1
+            batch = wins[i:j]
+            xb = _lib.empty((len(batch), C) + wdims, vol.dtype, dev)
+            for b, w in enumerate(batch):
+                xb[b].copy_(vol[0][(slice(None),) + tuple(slice(a, e) for a, e in zip(w['lo'], w['hi']))])
+            try:
+                out = model(xb)
+            except RuntimeError as e:   # (torch.OutOfMemoryError is one; native workspace failures say so)
+                if len(batch) == 1 or tiles_per_batch is not None or not _oom(e):
+                    raise
+                # the estimate was optimistic: retry this run of windows with half the batch
+                del xb
+                batch_cap = max(1, len(batch) // 2)
+                continue
+            if out.dim() != 5 or out.shape[1] < 5 or tuple(out.shape[2:]) != wdims or out.shape[0] != len(batch):
+                raise RuntimeError(f'predict_instance_mask: the model returned {tuple(out.shape)} for a batch of '
+                                   f'{len(batch)} windows of {wdims}; expected at least 5 channels '
+                                   '(probability, -, three vector components) of the window\'s size')
+            for b, w in enumerate(batch):
+                t, code, stride = instances._planes(out[b, 2:5], dev, 'predict_instance_mask')
+                got = instances.paste_window(t, code, stride, out[b, 0] > mask_threshold, w, labels, count + 1,
+                                             sigma, num_peaks)
+                centres.append(got)
+                count += len(got)
+            i = j
+    print(f'Predicted {count} cell from runet output')
+    return labels.view((1, 1) + shape), np.concatenate(centres).reshape(-1, 3)
 
 
 def predict_segmentation_mask(unet, image, device=None, use_probability_map=False,

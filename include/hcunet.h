@@ -650,6 +650,21 @@ int hcu_peak_candidates(const double *h, int X, int Y, int Z, int32_t *cand_inde
 int hcu_vec_label(const void *vec, int dtype, int64_t chan_stride, int X, int Y, int Z, const int32_t *peaks,
                   int n, const void *mask, int mask_dtype, int label_offset, double *label,
                   hcu_stream_t stream);
+/* One window of a tiled stack (hcunet_amd/instances.py: stitch_vec_to_cell).
+ * vec, the peaks and the mask are the window's own, [X][Y][Z], window-local
+ * coordinates; dst is the stack's int32 label volume [DX][DY][DZ] (below 2^31
+ * voxels too) and (ox, oy, oz) the window's origin in it; the window must lie
+ * inside dst (HCU_ERR_SHAPE).  The winner of a voxel is hcu_vec_label's.
+ * ids: device int32 [n], the stack-wide id of each peak, 0 for a peak another
+ * window owns.  bounds: HOST array {lo0, hi0, lo1, hi1, lo2, hi2} of floats,
+ * +-Inf allowed, NaN HCU_ERR_INVALID.  dst[o + v] = ids[winner] iff a peak
+ * won, ids[winner] != 0, not float(mask[v]) < 0.2 (null: no mask) and
+ * lo_a <= floorf(c_a) < hi_a on every axis (compared as floats); every other
+ * voxel of dst is left as it is.  n = 0 writes nothing. */
+int hcu_vec_label_paste(const void *vec, int dtype, int64_t chan_stride, int X, int Y, int Z,
+                        const int32_t *peaks, const int32_t *ids, int n, const void *mask, int mask_dtype,
+                        const float *bounds, int32_t *dst, int DX, int DY, int DZ, int ox, int oy, int oz,
+                        hcu_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* Cell objects from a label volume (hcat/segment.py: generate_cell_objects
