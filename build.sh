@@ -6,14 +6,19 @@ cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 OUT=${OUT:-hcunet_amd/libhcunet.so}   # (OUT / BDIR: a variant build for A/B runs)
 BDIR=${BDIR:-build}
-SRC="hcunet_amd/csrc/timing.cpp hcunet_amd/csrc/families.cpp hcunet_amd/csrc/gconv.hip hcunet_amd/csrc/conv2.hip hcunet_amd/csrc/conv8.hip hcunet_amd/csrc/wgrad.hip hcunet_amd/csrc/wgrad8.hip hcunet_amd/csrc/wgrad3.hip hcunet_amd/csrc/pointwise.hip hcunet_amd/csrc/loss_adam.hip hcunet_amd/csrc/loss_ext.hip hcunet_amd/csrc/prep_all.hip hcunet_amd/csrc/bconv.hip hcunet_amd/csrc/bconv_f32.hip hcunet_amd/csrc/bconv_f32_cv1.hip hcunet_amd/csrc/bconv_f32_cv2.hip hcunet_amd/csrc/bconv_f32_cv4.hip hcunet_amd/csrc/bconv_bf16_cv1.hip hcunet_amd/csrc/bconv_bf16_cv2.hip hcunet_amd/csrc/bconv_bf16_cv4.hip hcunet_amd/csrc/bwgrad.hip hcunet_amd/csrc/segment.hip hcunet_amd/csrc/ingest.hip hcunet_amd/csrc/augment.hip hcunet_amd/csrc/targets.hip hcunet_amd/csrc/instances.hip hcunet_amd/csrc/cells.hip hcunet_amd/csrc/layout.hip hcunet_amd/csrc/pwconv.hip hcunet_amd/csrc/unet.cpp"
+SRC="hcunet_amd/csrc/timing.cpp hcunet_amd/csrc/families.cpp hcunet_amd/csrc/gconv.hip hcunet_amd/csrc/conv2.hip hcunet_amd/csrc/conv8.hip hcunet_amd/csrc/wgrad.hip hcunet_amd/csrc/wgrad8.hip hcunet_amd/csrc/wgrad3.hip hcunet_amd/csrc/pointwise.hip hcunet_amd/csrc/loss_adam.hip hcunet_amd/csrc/loss_ext.hip hcunet_amd/csrc/prep_all.hip hcunet_amd/csrc/bconv.hip hcunet_amd/csrc/bconv_f32.hip hcunet_amd/csrc/bconv_f32_cv1.hip hcunet_amd/csrc/bconv_f32_cv2.hip hcunet_amd/csrc/bconv_f32_cv4.hip hcunet_amd/csrc/bconv_bf16_cv1.hip hcunet_amd/csrc/bconv_bf16_cv2.hip hcunet_amd/csrc/bconv_bf16_cv4.hip hcunet_amd/csrc/bwgrad.hip hcunet_amd/csrc/segment.hip hcunet_amd/csrc/ingest.hip hcunet_amd/csrc/augment.hip hcunet_amd/csrc/targets.hip hcunet_amd/csrc/instances.hip hcunet_amd/csrc/cells.hip hcunet_amd/csrc/layout.hip hcunet_amd/csrc/pwconv.hip hcunet_amd/csrc/error.cpp hcunet_amd/csrc/layers.cpp hcunet_amd/csrc/exec.cpp hcunet_amd/csrc/unet.cpp hcunet_amd/csrc/chain.cpp hcunet_amd/csrc/ops.cpp"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Iinclude $*"
 mkdir -p "$BDIR"
 objs=()
 pids=()
 for s in $SRC; do
   o=$BDIR/$(basename "$s").o
-  if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ hcunet_amd/csrc/common.h -nt "$o" ] || [ hcunet_amd/csrc/bconv_kernel.h -nt "$o" ] || [ include/hcunet.h -nt "$o" ] || [ build.sh -nt "$o" ]; then
+  stale=0
+  if [ ! -f "$o" ]; then stale=1; fi
+  for dep in "$s" hcunet_amd/csrc/*.h include/hcunet.h build.sh; do   # (any internal header: no list to keep)
+    if [ "$dep" -nt "$o" ]; then stale=1; fi
+  done
+  if [ $stale -eq 1 ]; then
     lang=""
     case "$s" in *.cpp) lang="-x hip";; esac
     $HIPCC $lang $FLAGS -c "$s" -o "$o.tmp" && mv "$o.tmp" "$o" &

@@ -22,7 +22,7 @@ namespace hcu {
 
 // ---------------------------------------------------------------------------
 // Every kernel launch of the library goes through HCU_LAUNCH.  While a
-// chain record is armed (the backward, Ctx in unet.cpp), each kernel launched
+// chain record is armed (the backward, Ctx in exec.h), each kernel launched
 // on the chain stream carries the chain event as its stop event, so the
 // weight-gradient branch can wait on the chain's last kernel directly: no
 // marker packet on the chain (measured on MI355X with HCU_FORK_DUP: each

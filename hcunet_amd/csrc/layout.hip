@@ -1,4 +1,4 @@
-// Channels-last layout kernels of the layer-chain executor (unet.cpp,
+// Channels-last layout kernels of the layer-chain executor (chain.cpp,
 // hcu_chain_*): the dilation sub-lattice (space-to-batch) re-layouts that let a
 // large dilated Conv3d run as dilation-1 convolutions on its sub-grids
 // (hcat/r_unet.py:348-353: StackedDilation's 5^3 kernels at dilation 1..5),

@@ -2,6 +2,7 @@
 // and the Adam step (torch.optim.Adam as used in tests/r_unet_test.py:24,56).
 #include "common.h"
 #include "timing.h"
+#include "../../include/hcunet.h"
 #include <hip/hip_fp16.h>
 #include <algorithm>
 #include <cmath>
@@ -154,3 +155,40 @@ int launch_adam(float *p, const float *g, float *m, float *v, int64_t n, float l
 }
 
 }  // namespace hcu
+
+extern "C" {
+
+size_t hcu_loss_pixel_scratch_bytes(int64_t n_pred) {
+  return hcu::align_up((size_t)hcu::loss_rows(n_pred) * sizeof(float), 256);
+}
+
+int hcu_loss_pixel_fwd(const float *pred, int B, int C, int PX, int PY, int PZ, const void *mask,
+                       int mask_dtype, const void *pwl, int pwl_dtype, int MX, int MY, int MZ,
+                       float *loss, float *dpred, void *scratch, size_t scratch_bytes,
+                       hcu_stream_t stream) {
+  using namespace hcu;
+  if (!pred || !mask || !loss || !scratch) return fail(HCU_ERR_INVALID, "null argument");
+  if (MX < PX || MY < PY || MZ < PZ)
+    return fail(HCU_ERR_SHAPE, "mask/pwl smaller than the prediction");
+  if (mask_dtype < 0 || mask_dtype > 2 || pwl_dtype < 0 || pwl_dtype > 1)
+    return fail(HCU_ERR_INVALID, "unsupported mask/pwl dtype");
+  const int64_t n = (int64_t)B * C * PX * PY * PZ;
+  if (scratch_bytes < hcu_loss_pixel_scratch_bytes(n))
+    return fail(HCU_ERR_WORKSPACE, "loss scratch too small");
+  return launch_loss_pixel(pred, B, C, PX, PY, PZ, mask, mask_dtype, pwl, pwl_dtype, MX, MY, MZ,
+                           loss, dpred, (float *)scratch, loss_rows(n), (hipStream_t)stream);
+}
+
+int hcu_scale_by_device_scalar(const float *src, const float *scale, float *dst, int64_t n,
+                               hcu_stream_t stream) {
+  return hcu::launch_scale(src, scale, dst, n, (hipStream_t)stream);
+}
+
+int hcu_adam_step(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1,
+                  float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
+                  hcu_stream_t stream) {
+  return hcu::launch_adam(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
+                          (hipStream_t)stream);
+}
+
+}  // extern "C"

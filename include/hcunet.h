@@ -179,7 +179,9 @@ int hcu_unet_plan_bn_layers(const hcu_unet_plan *plan, hcu_bn_layer_info *out, i
 /* BatchNorm + ReLU applied); parameters / gradients live in flat fp32       */
 /* buffers at the per-op offsets; BatchNorm running statistics are passed    */
 /* per BatchNorm op (hcu_unet_tensors' arrays, in op order).  Plans are      */
-/* hcu_unet_plan objects (hcu_unet_plan_destroy frees them).                 */
+/* hcu_unet_plan objects (hcu_unet_plan_destroy frees them); a handle of the */
+/* other kind is refused with HCU_ERR_INVALID by hcu_chain_* and hcu_unet_*  */
+/* alike (hcu_unet_plan_query and hcu_unet_plan_destroy take both).          */
 /* ------------------------------------------------------------------------ */
 enum { HCU_CHAIN_CONV = 0, HCU_CHAIN_POOL = 1, HCU_CHAIN_CONVT = 2 };
 #define HCU_CHAIN_MAX_OPS 16

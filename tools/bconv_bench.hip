@@ -44,7 +44,7 @@ BENCH_STUB(float, 1) BENCH_STUB(float, 2) BENCH_STUB(uint16_t, 1) BENCH_STUB(uin
 #include <vector>
 
 namespace hcu {
-// the library's error channel (unet.cpp), stand-alone here
+// the library's error channel (error.cpp), stand-alone here
 void set_error(const std::string &msg) { fprintf(stderr, "error: %s\n", msg.c_str()); }
 int fail(int code, const std::string &msg) {
   set_error(msg);

@@ -11,7 +11,7 @@
 #include <vector>
 #include "hcunet.h"
 
-namespace hcu {   // the two error helpers of unet.cpp, which this program does not link
+namespace hcu {   // the two error helpers of error.cpp, which this program does not link
 static thread_local std::string g_err;
 void set_error(const std::string &msg) { g_err = msg; }
 int fail(int code, const std::string &msg) {
